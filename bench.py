@@ -9,8 +9,14 @@ token ids, per-sample seeded latents) are resident in HBM before the timed
 region.  Synthetic inputs and seeded random weights of the SD1.5 / CLAP HTSAT
 architectures (no network, no checkpoints).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds the side
+measurements to that line: the dominant-kernel roofline and the per-family ledger, the rocprofv3 PMC
+traffic passes, the c1 / c2 / c5 configs on the GPU and the fp32 CPU baseline (each with its own
+--no-* switch).  --dump-outputs DIR writes what the last timed step returned (images.npy, and the
+final latents it decoded, latents.npy) as float32 for output-for-output comparison of two builds.
 """
 from __future__ import annotations
 
@@ -243,6 +249,22 @@ def gpu_config_runs(pipe, dev, log):
     return out
 
 
+DUMP_MAX_ELEMS = 7 * 2 ** 20   # float32 elements per dumped array (28 MiB): the two arrays stay under 64 MB
+
+
+def dump_outputs(path: Path, arrays: dict) -> None:
+    """Write each tensor as path/<name>.npy in float32.  An array above DUMP_MAX_ELEMS is written as a
+    fixed sample of its flattened elements (indices drawn once from seed 0, sorted), so two runs with the
+    same arguments write the same positions."""
+    path.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(path / f"{name}.npy", t.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -251,12 +273,18 @@ def main():
     ap.add_argument("--batch", type=int, default=8, help="images per GPU")
     ap.add_argument("--ddim-steps", type=int, default=50)
     ap.add_argument("--res", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC traffic passes")
-    ap.add_argument("--no-configs", action="store_true", help="skip the c1/c2/c5 side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's images and final latents as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline / ledger, PMC traffic, the c1/c2/c5 configs and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the fp32 CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 PMC traffic passes")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the c1/c2/c5 side measurements")
     ap.add_argument("--dtype", default="fp16", choices=["fp16"],
                     help="compute dtype of the HIP path (fp16 storage, fp32 accumulation; the only one built)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from clap2diffusion_amd import distributed as D
     from clap2diffusion_amd.pipeline import AudioToImageInference
@@ -283,33 +311,39 @@ def main():
         ctx.all_gather(img, gathered)
         return img
 
-    dt, _ = D.timed_run(ctx, one_batch, a.steps, a.warmup, torch.cuda.synchronize,
-                        log=lambda m: log("[bench] " + m))
+    dt, img = D.timed_run(ctx, one_batch, a.steps, a.warmup, torch.cuda.synchronize,
+                          log=lambda m: log("[bench] " + m))
     finite = bool(torch.isfinite(pipe.last_denoiser.x).all().item())
     ms_per_step = dt / a.steps * 1e3
     total_images = ctx.world * B * a.steps
     value = total_images / dt
 
     if ctx.rank == 0:
-        roof = measure_dominant_kernel(dev)
+        if a.dump_outputs:
+            # what the last timed step handed back: the uint8 images (every rank's, in rank order, for
+            # world > 1) and the final latents of this rank that the VAE decoded into them
+            dump_outputs(Path(a.dump_outputs), {"images": torch.cat(gathered) if ctx.world > 1 else img,
+                                                "latents": pipe.last_denoiser.x})
         unet_tf = UNET_GFLOP_PER_SAMPLE * (a.res / 512) ** 2 * 2 * a.ddim_steps * total_images / dt / 1e3
+        roof, extra, cpu = {}, {}, None
+        if a.full:
+            roof = measure_dominant_kernel(dev)
+            n_, h_, c_ = 16, 64, 320
+            # padded x + resid + out + weights
+            roof["algorithmic_bytes"] = 2 * (n_ * (h_ + 2) ** 2 * c_ + 2 * n_ * h_ * h_ * c_ + c_ * 9 * c_)
+            try:
+                roof["family_frac"], fam_meta = family_fractions(pipe.last_denoiser)
+                roof.update(fam_meta)
+            except Exception as e:  # noqa: BLE001 - reported, never fatal to the bench
+                roof["family_frac"], roof["family_source"] = None, f"ledger failed: {type(e).__name__}: {e}"
+            if not a.no_pmc and ctx.world == 1:
+                tr, src = pmc_traffic()
+                roof["traffic"] = None if tr is None else round(tr)
+                roof["traffic_source"] = src
+            if not a.no_configs and ctx.world == 1 and (a.res, B) == (512, 8):
+                extra = gpu_config_runs(pipe, dev, log)
+            cpu = None if (a.no_cpu_baseline or ctx.world > 1) else cpu_baseline()
         roof["pipeline_unet_tflops"] = round(unet_tf, 2)
-        n_, h_, c_ = 16, 64, 320
-        # padded x + resid + out + weights
-        roof["algorithmic_bytes"] = 2 * (n_ * (h_ + 2) ** 2 * c_ + 2 * n_ * h_ * h_ * c_ + c_ * 9 * c_)
-        try:
-            roof["family_frac"], fam_meta = family_fractions(pipe.last_denoiser)
-            roof.update(fam_meta)
-        except Exception as e:  # noqa: BLE001 - reported, never fatal to the bench
-            roof["family_frac"], roof["family_source"] = None, f"ledger failed: {type(e).__name__}: {e}"
-        if not a.no_pmc and ctx.world == 1:
-            tr, src = pmc_traffic()
-            roof["traffic"] = None if tr is None else round(tr)
-            roof["traffic_source"] = src
-        extra = {}
-        if not a.no_configs and ctx.world == 1 and (a.res, B) == (512, 8):
-            extra = gpu_config_runs(pipe, dev, log)
-        cpu = None if (a.no_cpu_baseline or ctx.world > 1) else cpu_baseline()
         # BASELINE.json configs: c3 is the default line; other shapes are labelled, not the metric
         cfg_name = {(512, 8): "c3", (512, 1): "c2", (768, 4): "c5"}.get((a.res, B), "custom")
         if ctx.world > 1 and (a.res, B) == (512, 8):
@@ -318,7 +352,7 @@ def main():
             "metric": "512x512 images/sec @ 50 DDIM steps, batch=8, 1/2/4/8 MI355X",
             "value": round(value, 4), "unit": "images/sec", "n_gpus": ctx.world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": round(ms_per_step, 2), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": a.dtype,
+            "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "full": a.full,
             "data": "synthetic (seeded thunder-like audio, fixed token ids, random-init SD1.5/CLAP weights)",
             "config": {"workload": f"{cfg_name}: batch={B}/GPU, {a.ddim_steps} DDIM steps, {a.res}x{a.res}, CFG 7.5, "
                                    "log-mel+HTSAT+projectors+CLIP+UNet+VAE, all-gather of images",

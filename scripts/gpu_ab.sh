@@ -9,13 +9,14 @@
 #   CMD=norm   each arm runs scripts/bench_norm_graph.py (graph-replayed GN / LN shapes)
 #   CMD=shapes each arm runs scripts/unet_shapes.py (per-shape GEMM breakdown)
 #   CMD=attn   each arm runs scripts/bench_attn.py (the UNet attention shapes, random operands)
-#   CMD=bench  (default) the bench line with BENCH_ARGS (default: short, no CPU / PMC / configs)
+#   CMD=bench  (default) the bench line with --full BENCH_ARGS (default: short, no CPU / PMC / configs)
 # PYTEST_K (optional): run that -m gpu subset once per arm first.  Stops at the first failure.
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 mkdir -p gpurun_out/ab
 BENCH_ARGS=${BENCH_ARGS:---steps 2 --warmup 1 --no-cpu-baseline --no-pmc --no-configs}
+BENCH_ARGS="--full $BENCH_ARGS"   # the arms print the roofline / c2 / c5 legs, which bench.py measures under --full
 arm() {  # label, comma-separated env, command...
   local label=$1 envs=$2; shift 2
   (

@@ -9,15 +9,16 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 mkdir -p gpurun_out/prof
 if [ -z "$NOBENCH" ]; then
+  BENCH_ARGS="--full $BENCH_ARGS"   # the bench line with its side measurements
   timeout -k 10 ${BENCH_TIMEOUT:-500} python -u bench.py $BENCH_ARGS > gpurun_out/bench.json 2> gpurun_out/bench.err
   rc=$?; tail -4 gpurun_out/bench.err; cat gpurun_out/bench.json
   [ $rc -eq 0 ] || exit $rc
 fi
 for cfg in ${TRACES-c3 c2}; do
   case $cfg in
-    c3) A="--batch 8" ;;
-    c2) A="--batch 1" ;;
-    c5) A="--batch 4 --res 768" ;;
+    c3) A="--full --batch 8" ;;
+    c2) A="--full --batch 1" ;;
+    c5) A="--full --batch 4 --res 768" ;;
     *) echo "unknown config $cfg"; exit 1 ;;
   esac
   P=/tmp/prof_$cfg; rm -rf $P; mkdir -p $P

@@ -12,6 +12,7 @@ rc=$?
 echo "pytest exit $rc"; grep -E "PASSED|FAILED|ERROR" gpurun_out/pytest_gpu.log | tail -3; tail -5 gpurun_out/pytest_gpu.log
 case $rc in 0|1) ;; *) exit $rc ;; esac
 [ -n "$NOBENCH" ] && exit $rc
+set -- --full "$@"   # the bench line with its side measurements (roofline, PMC, configs, CPU baseline)
 timeout -k 10 ${BENCH_TIMEOUT:-500} python -u bench.py "$@" > gpurun_out/bench.json 2> gpurun_out/bench.err
 rc=$?
 tail -5 gpurun_out/bench.err; cat gpurun_out/bench.json

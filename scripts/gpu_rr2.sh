@@ -10,5 +10,6 @@ for lib in ${ATTN_LIBS}; do
   echo "== attention $lib"
   C2D_LIB=$PWD/clap2diffusion_amd/$lib.so timeout -k 10 200 python -u scripts/bench_attn.py 2>&1 | grep -v amdgpu.ids || exit 1
 done
-timeout -k 10 500 python -u bench.py --no-cpu-baseline --no-pmc > gpurun_out/bench.json 2> gpurun_out/bench.err; rc=$?
-tail -3 gpurun_out/bench.err; cat gpurun_out/bench.json; exit $rc
+OUT=${BENCH_OUT:-bench_out}; mkdir -p "$OUT"
+timeout -k 10 500 python -u bench.py --full --no-cpu-baseline --no-pmc > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
+tail -3 "$OUT/bench.err"; cat "$OUT/bench.json"; exit $rc
