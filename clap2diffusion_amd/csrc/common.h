@@ -68,6 +68,9 @@ extern thread_local int g_last_hip_error;
 #ifndef C2D_TUNE_TAIL_SPLIT
 #define C2D_TUNE_TAIL_SPLIT 1       // 0: no image split of a quantisation tail
 #endif
+#ifndef C2D_TUNE_UPFOLD
+#define C2D_TUNE_UPFOLD 1           // 0: no folded-upsample conv (c2d_conv_desc::up = 2 is C2D_E_SHAPE; callers materialise the x2 tensor)
+#endif
 #ifndef C2D_TUNE_PANEL_REGB
 #define C2D_TUNE_PANEL_REGB 0       // 1: the K = 320 panel GEMM loads its weights into registers
 #endif

@@ -77,7 +77,8 @@ struct EpiPass {
     }
 
     // one chunk: act(image) [+ temb] [+ residual] -> fp16 -> store (predicated)
-    __device__ __forceinline__ static void body(const IgemmParams& p, const float* img, int pitchf, int row, int sc,
+    template <class P>   // IgemmParams, or IgemmParamsFold with its output row map (out_row)
+    __device__ __forceinline__ static void body(const P& p, const float* img, int pitchf, int row, int sc,
                                                 int m, int j, bool ok, const hv& rr, const hv& tt) {
         const float* src = img + row * pitchf + sc;
         float v[W];
@@ -116,7 +117,7 @@ struct EpiPass {
         hv o;
 #pragma unroll
         for (int q = 0; q < W; ++q) o[q] = (f16)v[q];
-        if (ok) *reinterpret_cast<hv*>(p.out + (size_t)m * p.out_ld + j) = o;
+        if (ok) *reinterpret_cast<hv*>(p.out + out_row(p, m) * p.out_ld + j) = o;
         if constexpr (WB) {
             float* dst = const_cast<float*>(src);
 #pragma unroll
@@ -125,7 +126,8 @@ struct EpiPass {
         }
     }
 
-    __device__ __forceinline__ void finish(const IgemmParams& p, const float* img, int pitchf, int m0, int jp0,
+    template <class P>
+    __device__ __forceinline__ void finish(const P& p, const float* img, int pitchf, int m0, int jp0,
                                            int lane) const {
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
@@ -140,7 +142,8 @@ struct EpiPass {
     // with its image read (one wait per chunk, two chunks per trip); for kernels whose
     // epilogue code runs from a cold instruction cache once per tile (the unrolled
     // prefetch form grew their code past the short-branch range and ran slower)
-    __device__ __forceinline__ static void compact(const IgemmParams& p, const float* img, int pitchf, int m0,
+    template <class P>
+    __device__ __forceinline__ static void compact(const P& p, const float* img, int pitchf, int m0,
                                                    int jp0, int lane) {
         const int hw = p.oh * p.ow;
         const int n_all = (RG == 0 && (hw % ROWS) == 0) ? m0 / hw : -1;
@@ -161,8 +164,8 @@ struct EpiPass {
 // one pass: prefetch the pass's residual / temb, let the kernel write the image
 // (write_img(): bias-added accumulators -> LDS, this wave's rows only), wait for the
 // LDS writes, finish.  The wave reads back only its own image, so a wave barrier suffices.
-template <bool COMPACT, int NT, int RG, int W, bool GG, int ROWS, int COLS, int RES, int TEMB, class WriteImg>
-__device__ __forceinline__ void epi_pass_t(const IgemmParams& p, const float* img, int pitchf, int m0, int jp0,
+template <bool COMPACT, int NT, int RG, int W, bool GG, int ROWS, int COLS, int RES, int TEMB, class P, class WriteImg>
+__device__ __forceinline__ void epi_pass_t(const P& p, const float* img, int pitchf, int m0, int jp0,
                                            int lane, WriteImg&& write_img) {
     typedef EpiPass<W, GG, ROWS, COLS, RES, TEMB, NT, RG> EP;
     auto sync = [&]() __attribute__((always_inline)) {
@@ -260,8 +263,8 @@ __device__ __forceinline__ void epi_gn_moments(const IgemmParams& p, float* img,
 
 // ROWS x COLS image pass -> outputs; picks the 16-B (W = 8) form when the output
 // width, the leading dimensions and the base addresses allow it
-template <int ROWS, int COLS, bool COMPACT, int NT = 64, int RG = 0, class WriteImg>
-__device__ __forceinline__ void epi_pass(const IgemmParams& p, const float* img, int pitchf, int m0, int jp0,
+template <int ROWS, int COLS, bool COMPACT, int NT = 64, int RG = 0, class P, class WriteImg>
+__device__ __forceinline__ void epi_pass(const P& p, const float* img, int pitchf, int m0, int jp0,
                                          int lane, WriteImg&& w) {
     const bool gg = p.act == C2D_ACT_GEGLU;
     const int out_cols = gg ? (p.cout >> 1) : p.cout;
@@ -316,8 +319,8 @@ __device__ __forceinline__ f32x4 bias4(const IgemmParams& p, int j) {
 // The image geometry and the GEGLU flag are template parameters so the chunk ->
 // (row, column) split is constant-divisor arithmetic: with run-time divisors the
 // integer divisions cost as much VALU per chunk as the GELU itself.
-template <int W, bool GG, int ROWS, int COLS>
-__device__ __forceinline__ void epi_rows_plain_t(const IgemmParams& p, const float* img, int pitchf, int m0, int jp0,
+template <int W, bool GG, int ROWS, int COLS, class P>
+__device__ __forceinline__ void epi_rows_plain_t(const P& p, const float* img, int pitchf, int m0, int jp0,
                                            int lane) {
     typedef _Float16 hv __attribute__((ext_vector_type(W)));
     constexpr int CPR = GG ? COLS / (2 * W) : COLS / W;   // W-wide output chunks per row
@@ -396,14 +399,14 @@ __device__ __forceinline__ void epi_rows_plain_t(const IgemmParams& p, const flo
         hv o;
 #pragma unroll
         for (int r = 0; r < W; ++r) o[r] = (f16)v[r];
-        *reinterpret_cast<hv*>(p.out + (size_t)m * p.out_ld + j) = o;
+        *reinterpret_cast<hv*>(p.out + out_row(p, m) * p.out_ld + j) = o;
     }
 }
 
 // ROWS x COLS fp32 image -> outputs; picks the 16-B (W = 8) form when the output
 // width, the leading dimensions and the base addresses allow it
-template <int ROWS, int COLS>
-__device__ __forceinline__ void epi_rows_plain(const IgemmParams& p, const float* img, int pitchf, int m0, int jp0,
+template <int ROWS, int COLS, class P>
+__device__ __forceinline__ void epi_rows_plain(const P& p, const float* img, int pitchf, int m0, int jp0,
                                          int lane) {
     const bool gg = p.act == C2D_ACT_GEGLU;
     const int out_cols = gg ? (p.cout >> 1) : p.cout;

@@ -61,9 +61,60 @@ struct IgemmParams {
     int gn_cpg;      // channels per group of gn_mom
 };
 
+// Folded nearest-x2 upsample + 3x3 (c2d_conv_desc::up = 2): the layer is four 2x2 convs of the low-res
+// image, one per output phase (a, b) = (oy & 1, ox & 1), K ordered (ty, tx, cin) over the phase's own
+// folded weights.  The kernels that take it (template KS == 2) run it as one GEMM of 4 x M rows: p.oh x p.ow
+// is the low-res grid, p.M the rows of one phase, and row tile mt serves phase mt & 3 of spatial tile mt >> 2
+// (the four phases of a tile are neighbours in block order and read the same A slab).  Each workgroup keeps
+// its own copy of the parameters with its phase: weights advanced to the phase's pack, and the output row
+// map below.  Every other kernel passes plain IgemmParams, for which out_row is the identity at compile time.
+struct IgemmParamsFold : IgemmParams {
+    int ph;        // output phase 2 a + b of this workgroup
+    float rcp_w;   // 1 / w
+};
+
+// output row of GEMM row m
+__device__ __forceinline__ size_t out_row(const IgemmParams&, int m) { return (size_t)m; }
+// phase ph, low-res pixel m = (n h + i) w + j  ->  (n 2h + 2i + a) 2w + 2j + b.  m < 2^24 (checked on the
+// host), so the float quotient estimate is off by at most one
+__device__ __forceinline__ size_t out_row_ph(const IgemmParams& p, int m, int ph, float rcp_w) {
+    int q = (int)((float)m * rcp_w);
+    int r = m - q * p.w;
+    if (r < 0) { --q; r += p.w; }
+    if (r >= p.w) { ++q; r -= p.w; }
+    return (size_t)((2 * q + (ph >> 1)) * 2 * p.w + 2 * r + (ph & 1));
+}
+__device__ __forceinline__ size_t out_row(const IgemmParamsFold& p, int m) { return out_row_ph(p, m, p.ph, p.rcp_w); }
+
+// the parameters a kernel works with: the kernel argument itself, or (folded upsample) its per-workgroup copy
+template <bool FOLD>
+struct KernelParams {
+    const IgemmParams& p;
+    __device__ __forceinline__ explicit KernelParams(const IgemmParams& k) : p(k) {}
+};
+template <>
+struct KernelParams<true> {
+    IgemmParamsFold p;
+    __device__ __forceinline__ explicit KernelParams(const IgemmParams& k) {
+        static_cast<IgemmParams&>(p) = k;
+        p.ph = 0;
+        p.rcp_w = 1.0f / (float)k.w;
+    }
+    // row tile mt of the grid -> this workgroup's phase (weights, row map) and its spatial row tile
+    __device__ __forceinline__ int set_phase(int mt) {
+        p.ph = mt & 3;
+        p.wt += (size_t)p.ph * p.cout * p.kpad;
+        return mt >> 2;
+    }
+};
+
 // one accumulator quad of K slice `slice` into the split-K workspace, fp32 or rounded to fp16
-__device__ __forceinline__ void store_partial(const IgemmParams& p, int slice, int m, int j, const f32x4& v) {
-    const size_t off = ((size_t)slice * p.M + m) * p.cout + j;
+// (folded upsample: the slabs hold 4 p.M virtual rows, phase ph at ph * p.M)
+template <class P>
+__device__ __forceinline__ void store_partial(const P& p, int slice, int m, int j, const f32x4& v) {
+    size_t row = (size_t)slice * p.M + m;
+    if constexpr (std::is_same<P, IgemmParamsFold>::value) row = ((size_t)slice * 4 + p.ph) * p.M + m;
+    const size_t off = row * p.cout + j;
     if (p.slab16) {
         const f16x4 h = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
         *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(p.ws) + off) = h;
@@ -213,7 +264,7 @@ __device__ __forceinline__ void epilogue_tiles(const IgemmParams& p, f32x4 (&acc
                 f16x4 o;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) o[r] = (f16)v[r];
-                if (mok[b] && cok[a]) *reinterpret_cast<f16x4*>(p.out + (size_t)mrow[b] * p.out_ld + col[a]) = o;
+                if (mok[b] && cok[a]) *reinterpret_cast<f16x4*>(p.out + out_row(p, mrow[b]) * p.out_ld + col[a]) = o;
             }
         }
     } else {
@@ -253,7 +304,7 @@ __device__ __forceinline__ void epilogue_tiles(const IgemmParams& p, f32x4 (&acc
                     if (p.resid) v += (float)rv[b][q][r];
                     o[r] = (f16)v;
                 }
-                if (mok[b] && cok[q]) *reinterpret_cast<f16x4*>(p.out + (size_t)mrow[b] * p.out_ld + jo[q]) = o;
+                if (mok[b] && cok[q]) *reinterpret_cast<f16x4*>(p.out + out_row(p, mrow[b]) * p.out_ld + jo[q]) = o;
             }
         }
     }
@@ -454,8 +505,12 @@ __device__ __forceinline__ void epilogue_chunked(const IgemmParams& p, f32x4 (&a
 // order) and exit, group 0 adds them and runs the epilogue (or the split-K slab store).  Two
 // waves per SIMD on the under-filled grids (level-2 / level-3 GEMMs: one 4-wave tile per CU)
 // with no fp32 slab traffic and no combine launch.
+// KS = 2: the folded upsample (IgemmParamsFold): 4 taps (ty, tx) from the window origin (i + a - 1, j + b - 1)
 template <int WM, int WN, int TM, int TN, int STAGES, int KS, int KG = 1>
-__global__ void __launch_bounds__(64 * WM * WN * KG) igemm_dma_kernel(IgemmParams p) {
+__global__ void __launch_bounds__(64 * WM * WN * KG) igemm_dma_kernel(IgemmParams pk) {
+    KernelParams<KS == 2> kp(pk);
+    auto& p = kp.p;
+    constexpr int NT = KS * KS;   // taps
     constexpr int NW = WM * WN;
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
     constexpr int AI = BM / (8 * NW), BI = BN / (8 * NW);   // DMA pieces per wave per stage
@@ -472,12 +527,14 @@ __global__ void __launch_bounds__(64 * WM * WN * KG) igemm_dma_kernel(IgemmParam
     // block -> (output tile, K slice); the remap keeps a tile's slices on one XCD
     const int bid = xcd_remap(blockIdx.x, p.gx * p.gy * p.ksplit);
     const int tile = bid / p.ksplit, slice = bid - tile * p.ksplit;
-    const int mt = tile / p.gx, nt = tile - mt * p.gx;
+    int mt = tile / p.gx;
+    const int nt = tile - mt * p.gx;
+    if constexpr (KS == 2) mt = kp.set_phase(mt);
     const int m0 = mt * BM, n0 = nt * BN;
     const int lrow = lane >> 3, slot = lane & 7;
     const int hw = p.oh * p.ow;
     const bool two = p.c1 > 0;
-    const int pshift = KS == 3 ? p.w + 1 : 0;
+    const int pshift = KS >= 2 ? p.w + 1 : 0;
 
     // ---- per staged A row: byte offsets in each source + tap mask
     unsigned a_off0[AI], a_off1[AI], a_mask[AI];
@@ -489,7 +546,8 @@ __global__ void __launch_bounds__(64 * WM * WN * KG) igemm_dma_kernel(IgemmParam
         const int mm = m < p.M ? m : 0;
         const int nn = mm / hw, r = mm - nn * hw;
         const int oy = r / p.ow, ox = r - oy * p.ow;
-        const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
+        int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
+        if constexpr (KS == 2) { iy0 = oy + (p.ph >> 1) - 1; ix0 = ox + (p.ph & 1) - 1; }
         unsigned mask = 0;
         if (m < p.M) {
 #pragma unroll
@@ -527,17 +585,17 @@ __global__ void __launch_bounds__(64 * WM * WN * KG) igemm_dma_kernel(IgemmParam
     const char* u_wt = uniform_ptr(p.wt);
     // (tap, channel block) of the next issue; the packed weight column is tap * cin + cbase
     int tap = 0, cbase = kb * 64;
-    if (KS == 3) {
-        if (p.cmajor) { tap = kb % 9; cbase = (kb / 9) * 64; }
+    if (KS >= 2) {
+        if (p.cmajor) { tap = kb % NT; cbase = (kb / NT) * 64; }
         else { tap = cbase / p.cin; cbase -= tap * p.cin; }
     }
     auto issue = [&](int kt, int buf) {
         (void)kt;
         const int k0 = tap * p.cin + cbase;
-        const int ky = tap / 3, kx = tap - (tap / 3) * 3;
+        const int ky = tap / (KS == 2 ? 2 : 3), kx = tap - ky * (KS == 2 ? 2 : 3);
         const bool use1 = two && cbase >= p.c0;
         const int cs = use1 ? p.c1 : p.c0;
-        const unsigned sterm = 2u * (unsigned)((KS == 3 ? (ky * p.w + kx) * cs : 0) + (use1 ? cbase - p.c0 : cbase));
+        const unsigned sterm = 2u * (unsigned)((KS >= 2 ? (ky * p.w + kx) * cs : 0) + (use1 ? cbase - p.c0 : cbase));
         const char* sb = use1 ? u_src1 : u_src0;
         const unsigned bias = 2u * (unsigned)(pshift * cs);
         const unsigned sbytes = use1 ? bytes1 : bytes0;
@@ -556,11 +614,11 @@ __global__ void __launch_bounds__(64 * WM * WN * KG) igemm_dma_kernel(IgemmParam
 #pragma unroll
         for (int i = 0; i < BI; ++i)
             dma_piece(rb, base + A_BYTES + (wave * BI + i) * 1024, b_off[i]);
-        if (KS == 3 && p.cmajor) {                                 // taps inner
-            if (++tap == 9) { tap = 0; cbase += 64; }
+        if (KS >= 2 && p.cmajor) {                                 // taps inner
+            if (++tap == NT) { tap = 0; cbase += 64; }
         } else {                                                   // packed K order
             cbase += 64;
-            if (KS == 3 && cbase >= p.cin) { cbase = 0; ++tap; }
+            if (KS >= 2 && cbase >= p.cin) { cbase = 0; ++tap; }
         }
     };
 
@@ -703,7 +761,9 @@ __device__ __forceinline__ f32x4 slab_quad(const float* ws, size_t off) {
     }
 }
 
-template <int KS, bool S16>
+// FOLD: the folded upsample's slabs, p.M = 4 x the rows of a phase; virtual row m = phase * (p.M / 4) + low-res
+// pixel, stored through the phase's output row map
+template <int KS, bool S16, bool FOLD = false>
 __global__ void __launch_bounds__(256) splitk_reduce_kernel(IgemmParams p) {
     const int cq = p.cout >> 2;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -750,7 +810,12 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(IgemmParams p) {
         if (p.resid) v[r] += (float)rv[r];
         o[r] = (f16)v[r];
     }
-    *reinterpret_cast<f16x4*>(p.out + (size_t)m * p.out_ld + j) = o;
+    size_t orow = (size_t)m;
+    if constexpr (FOLD) {
+        const int mq = p.M >> 2, ph = m / mq;
+        orow = out_row_ph(p, m - ph * mq, ph, 1.0f / (float)p.w);
+    }
+    *reinterpret_cast<f16x4*>(p.out + orow * p.out_ld + j) = o;
 }
 
 // Split-K combine that also emits the output's GroupNorm moments (IgemmParams::gn_mom): block = kGnRb rows x
@@ -858,6 +923,24 @@ void run_splitk_reduce(const IgemmParams& p, hipStream_t s) {
 #undef C2D_SKG
         return;
     }
+#if C2D_TUNE_UPFOLD
+    if (p.up == 2) {   // folded upsample: 4 phases x p.M virtual rows (no moments, no residual / temb: validated)
+        IgemmParams q = p;
+        q.M = 4 * p.M;
+        const size_t total = (size_t)q.M * (q.cout >> 2);
+        const dim3 grid((unsigned)((total + 255) / 256)), blk(256);
+#define C2D_SKF(KS)                                                                               \
+    if (q.slab16) hipLaunchKernelGGL((splitk_reduce_kernel<KS, true, true>), grid, blk, 0, s, q); \
+    else hipLaunchKernelGGL((splitk_reduce_kernel<KS, false, true>), grid, blk, 0, s, q)
+        switch (q.ksplit) {
+            case 2: C2D_SKF(2); break;
+            case 4: C2D_SKF(4); break;
+            default: C2D_SKF(0); break;
+        }
+#undef C2D_SKF
+        return;
+    }
+#endif
     const size_t total = (size_t)p.M * (p.cout >> 2);
     const dim3 grid((unsigned)((total + 255) / 256)), blk(256);
 #define C2D_SKR(KS)                                                                   \
@@ -926,8 +1009,11 @@ template <int WM, int WN, int TM, int TN, int ST, int KG = 1>
 static void run_dma(IgemmParams& p, int ksize, int cout, hipStream_t s) {
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
     p.gx = (cout + BN - 1) / BN;
-    p.gy = (p.M + BM - 1) / BM;
+    p.gy = (p.M + BM - 1) / BM * (ksize == 2 ? 4 : 1);   // ksize 2: the folded upsample, every phase its own row tiles
     if (ksize == 1) launch_dma<WM, WN, TM, TN, ST, 1, KG>(p, s);
+#if C2D_TUNE_UPFOLD
+    else if (ksize == 2) launch_dma<WM, WN, TM, TN, ST, 2, KG>(p, s);
+#endif
     else launch_dma<WM, WN, TM, TN, ST, 3, KG>(p, s);
 }
 
@@ -1185,12 +1271,22 @@ static DmaPlan rr_plan(int id, int nk, int split) {
     return {id, (ncb + cbs - 1) / cbs, 9 * cbs};
 }
 
+// The folded upsample (c2d_conv_desc::up = 2) plans as a 3x3-class conv with K = 4 cin and M = 4 n h w, under
+// the table key ksize 2.  Its kernels: the ping-pong tiles 40 / 41 and the 16x16x32 LDS-DMA family; never the
+// row-ring tiles, the panel GEMM, the persistent tile or the 32x32 tiles.
+static int plan_ksize(const c2d_conv_desc* d) { return d->up == 2 ? 2 : d->ksize; }
+static bool fold_tile_ok(int id) {
+    return id == 40 || id == 41 || id == 7 || id == 1 || id == 2 || id == 3 || id == 8 || id == 9 || id == 80 || id == 81;
+}
+
 // rr_id: the row-ring tile this descriptor can run on (rr_tile), 0 = none
 static DmaPlan plan_for(long M, int cout, int kpad, int act, bool pps_ok, int ksize, int rr_id = 0,
                         bool panel_ok = false) {
     const bool geglu = act == C2D_ACT_GEGLU;
+    const bool fold = ksize == 2;
     const int nk = kpad / 64;
     int id = gemm_tile();
+    if (fold && !fold_tile_ok(id)) id = 0;   // a forced tile that does not take the mode: the planner's
     if (id == 70) {   // the panel GEMM (igemm_panel.h): one slice, no split
         if (panel_ok && gemm_split() <= 1) return {70, 1, nk};
         id = 0;
@@ -1240,7 +1336,7 @@ static DmaPlan plan_for(long M, int cout, int kpad, int act, bool pps_ok, int ks
     // stages (scripts/small_cout.py, forced tiles on one box: UNet conv_out 320 -> 4 at 64^2,
     // N = 16: 91.3 us on tile 40, 80.5 on the 64x64 tile 3, 49.0 on tile 29; VAE conv_out
     // 128 -> 4 at 512^2, N = 8: 1332.6 / 874.3 / 725.3 us)
-    if (cout <= 64 && !geglu) {
+    if (cout <= 64 && !geglu && !fold) {
         DmaPlan pl = plan_dma(M, cout, nk, geglu, 29, 0);
         if (pl.id == 29) return pl;
     }
@@ -1253,7 +1349,7 @@ static DmaPlan plan_for(long M, int cout, int kpad, int act, bool pps_ok, int ks
     if (!geglu && cout % 320 != 0) {
         const long mt = (M + 255) / 256;
         if (C2D_PP16_DEFAULT && cout % 256 == 0 && mt * (cout / 256) >= 192) return {41, 1, nk};   // ping-pong 256x256 (VAE 256/512 ch)
-        if (cout % 256 != 0 && cout % 128 == 0 && mt * (cout / 128) >= 192) return {29, 1, nk};
+        if (!fold && cout % 256 != 0 && cout % 128 == 0 && mt * (cout / 128) >= 192) return {29, 1, nk};
     }
     // 256x320: the ping-pong 16x16x32 kernel (tile 40, 5-12 % faster than the 32x32x16
     // tile 25 on every conv / K >= 320 GEMM shape measured, scripts/ab_tiles.py) except
@@ -1273,7 +1369,7 @@ static DmaPlan plan_for(long M, int cout, int kpad, int act, bool pps_ok, int ks
         }
         return {t256x320, 1, nk};
     }
-    if (nk >= 90 && t24 >= 64) {
+    if (nk >= (fold ? 40 : 90) && t24 >= 64) {
         DmaPlan pl = plan_dma(M, cout, nk, geglu, 25, 0);
         if (pl.id == 25) pl.id = t256x320;
         return pl;
@@ -1314,7 +1410,7 @@ static bool dma_eligible(const c2d_conv_desc* d) {
     const int amode = (d->ksize == 1) ? AM_1X1 : ((cin % 64) == 0 ? AM_3X3_FAST : AM_3X3_GEN);
     const int pd = d->src_pad ? 2 : 0;
     const size_t src_bytes = (size_t)d->n * (d->h + pd) * (d->w + pd) * (size_t)(d->c0 > d->c1 ? d->c0 : d->c1) * 2;
-    return (d->pro == C2D_PRO_NONE || d->pro == C2D_PRO_LNFOLD) && amode != AM_3X3_GEN && !d->up && gemm_mode() != 2 &&
+    return (d->pro == C2D_PRO_NONE || d->pro == C2D_PRO_LNFOLD) && amode != AM_3X3_GEN && d->up != 1 && gemm_mode() != 2 &&
            (d->c1 == 0 || (d->c0 & 63) == 0) && src_bytes < (1u << 31) &&
            (size_t)d->cout * d->kpad * 2 < (1u << 31);  // 32-bit buffer offsets
 }
@@ -1342,7 +1438,7 @@ static int rr_eligible(const c2d_conv_desc* d) {
 // deep K (>= 16 steps, so the extra launch is small against a round) and the planner's own choice
 // (no override); returns n1, 0 = no split.
 static int tail_images(const c2d_conv_desc* d, const DmaPlan& pl) {
-    if (pl.split != 1 || d->n < 2 || d->pro != C2D_PRO_NONE || d->kpad / 64 < 16) return 0;
+    if (pl.split != 1 || d->n < 2 || d->pro != C2D_PRO_NONE || d->kpad / 64 < 16 || d->up == 2) return 0;
     if (plan_override_tile() || plan_override_split() || !tuning().tail_split) return 0;
     const DmaTile* t = nullptr;
     for (const DmaTile& x : kDmaTiles)
@@ -1376,16 +1472,30 @@ static c2d_conv_desc tail_desc(const c2d_conv_desc* d, int n1) {
 static size_t tail_ws_bytes(const c2d_conv_desc* d, int n1) {
     const c2d_conv_desc t = tail_desc(d, n1);
     const long Mt = (long)t.n * t.oh * t.ow;
-    const DmaPlan tp = plan_for(Mt, t.cout, t.kpad, t.act, pps_eligible(&t), t.ksize, rr_eligible(&t), panel_eligible(&t));
+    const DmaPlan tp = plan_for(Mt, t.cout, t.kpad, t.act, pps_eligible(&t), plan_ksize(&t), rr_eligible(&t), panel_eligible(&t));
     return tp.split > 1 ? (size_t)tp.split * Mt * t.cout * sizeof(float) : 0;
+}
+
+// c2d_conv_desc::up = 2 (folded upsample): what the mode takes; C2D_OK or the code c2d_conv2d_igemm returns
+static int fold_check(const c2d_conv_desc* d) {
+    if (!C2D_TUNE_UPFOLD) return C2D_E_SHAPE;
+    if (d->ksize != 3 || d->stride != 1 || d->c1 != 0 || d->src1) return C2D_E_SHAPE;
+    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->oh != 2 * d->h || d->ow != 2 * d->w) return C2D_E_SHAPE;
+    if (d->c0 <= 0 || (d->c0 & 63) || d->kpad != 4 * d->c0 || d->cout <= 0 || (d->cout & 3)) return C2D_E_SHAPE;
+    if ((long)d->n * d->h * d->w >= (1L << 24)) return C2D_E_SHAPE;   // the row map's float quotient (out_row_ph)
+    if (d->src_pad || d->pro != C2D_PRO_NONE || d->act != C2D_ACT_NONE || d->temb || d->resid) return C2D_E_ARG;
+    if (d->gn_mom) return C2D_E_SHAPE;   // c2d_conv2d_gn_rows is 0: the consumer runs its own statistics pass
+    if (!dma_eligible(d)) return C2D_E_SHAPE;   // 32-bit buffer offsets; there is no other kernel for the mode
+    return C2D_OK;
 }
 
 extern "C" size_t c2d_conv2d_igemm_workspace_size(const c2d_conv_desc* d) {
     if (!d || d->ksize < 1 || d->oh <= 0 || d->ow <= 0 || d->n <= 0 || d->cout <= 0 || d->kpad < 64) return 0;
+    if (d->up == 2 && fold_check(d) != C2D_OK) return 0;
     if (!dma_eligible(d)) return 0;
     if (d->pro == C2D_PRO_LNFOLD) return 0;   // the panel GEMM, one slice
     const long M = (long)d->n * d->oh * d->ow;
-    const DmaPlan pl = plan_for(M, d->cout, d->kpad, d->act, pps_eligible(d), d->ksize, rr_eligible(d), panel_eligible(d));
+    const DmaPlan pl = plan_for(M, d->cout, d->kpad, d->act, pps_eligible(d), plan_ksize(d), rr_eligible(d), panel_eligible(d));
     if (const int n1 = tail_images(d, pl)) return tail_ws_bytes(d, n1);
     return pl.split > 1 ? (size_t)pl.split * M * d->cout * sizeof(float) : 0;
 }
@@ -1401,14 +1511,14 @@ static bool gn_split_ok(int ks) {   // the slice counts splitk_reduce_gn_kernel 
 }
 
 static int gn_rows_for(const c2d_conv_desc* d) {
-    if (!d || d->gn_groups <= 0 || d->cout % d->gn_groups) return 0;
+    if (!d || d->gn_groups <= 0 || d->cout % d->gn_groups || d->up == 2) return 0;
     const int cpg = d->cout / d->gn_groups;
     if (320 % cpg || d->cout % 320 || d->act != C2D_ACT_NONE) return 0;
     if ((d->out_ld & 7) || (d->resid && (d->resid_ld & 7)) || (d->temb && (d->temb_ld & 7)) || d->out_ld < d->cout) return 0;
     if (((uintptr_t)d->out | (uintptr_t)d->resid | (uintptr_t)d->temb) & 15) return 0;
     if (d->ksize < 1 || d->oh <= 0 || d->ow <= 0 || d->n <= 0 || d->kpad < 64 || !dma_eligible(d)) return 0;
     const long M = (long)d->n * d->oh * d->ow;
-    DmaPlan pl = plan_for(M, d->cout, d->kpad, d->act, pps_eligible(d), d->ksize, rr_eligible(d), panel_eligible(d));
+    DmaPlan pl = plan_for(M, d->cout, d->kpad, d->act, pps_eligible(d), plan_ksize(d), rr_eligible(d), panel_eligible(d));
     if (pl.id == 50 || pl.id == 70) return 0;   // the persistent / panel tiles never split and emit none
     bool split = false;
     if (pl.split > 1) {
@@ -1434,6 +1544,10 @@ extern "C" int c2d_conv2d_gn_rows(const c2d_conv_desc* d) { return gn_rows_for(d
 extern "C" int c2d_conv2d_igemm_plan(const c2d_conv_desc* d, int* tile_id, int* ksplit) {
     if (!d || !tile_id || !ksplit) return C2D_E_ARG;
     if (d->ksize < 1 || d->oh <= 0 || d->ow <= 0 || d->n <= 0 || d->cout <= 0 || d->kpad < 64) return C2D_E_SHAPE;
+    if (d->up == 2) {   // folded upsample: as the launch validates it
+        const int rc = fold_check(d);
+        if (rc != C2D_OK) return rc;
+    }
     if (d->pro == C2D_PRO_LNFOLD) {   // the panel GEMM or nothing (c2d_conv2d_igemm rejects the rest the same way)
         if (!panel_eligible(d)) return C2D_E_SHAPE;
         *tile_id = 70;
@@ -1446,7 +1560,7 @@ extern "C" int c2d_conv2d_igemm_plan(const c2d_conv_desc* d, int* tile_id, int* 
         return C2D_OK;
     }
     const long M = (long)d->n * d->oh * d->ow;
-    DmaPlan pl = plan_for(M, d->cout, d->kpad, d->act, pps_eligible(d), d->ksize, rr_eligible(d), panel_eligible(d));
+    DmaPlan pl = plan_for(M, d->cout, d->kpad, d->act, pps_eligible(d), plan_ksize(d), rr_eligible(d), panel_eligible(d));
     if (pl.split > 1) {
         const size_t need = (size_t)pl.split * M * d->cout * sizeof(float);
         if (!(d->ws && d->ws_bytes >= need && aligned16(d->ws))) pl.split = 1;
@@ -1461,11 +1575,16 @@ static int conv_run(const c2d_conv_desc* d, hipStream_t s, const DmaPlan* fixed)
 extern "C" int c2d_conv2d_igemm(const c2d_conv_desc* d, void* stream) {
     if (!d || !d->src0 || !d->weight || !d->out) return C2D_E_ARG;
     hipStream_t s = (hipStream_t)stream;
+    if (d->up < 0 || d->up > 2) return C2D_E_ARG;
+    if (d->up == 2) {   // folded upsample: everything it does not take is refused here, nothing launched
+        const int rc = fold_check(d);
+        if (rc != C2D_OK) return rc;
+    }
     if (d->gn_mom && gn_rows_for(d) == 0) return C2D_E_SHAPE;   // moments requested of a plan that cannot emit them
     if (d->gn_mom && ((uintptr_t)d->gn_mom & 7)) return C2D_E_ALIGN;
     if (d->n >= 2 && d->ksize >= 1 && d->oh > 0 && d->ow > 0 && d->cout > 0 && d->kpad >= 64 && dma_eligible(d)) {
         const long M = (long)d->n * d->oh * d->ow;
-        const DmaPlan pl = plan_for(M, d->cout, d->kpad, d->act, pps_eligible(d), d->ksize, rr_eligible(d), panel_eligible(d));
+        const DmaPlan pl = plan_for(M, d->cout, d->kpad, d->act, pps_eligible(d), plan_ksize(d), rr_eligible(d), panel_eligible(d));
         if (const int n1 = tail_images(d, pl)) {   // quantisation tail: whole rounds, then the rest
             c2d_conv_desc head = *d;
             head.n = n1;
@@ -1486,7 +1605,8 @@ static int conv_run(const c2d_conv_desc* d, hipStream_t s, const DmaPlan* fixed)
     const int cin = d->c0 + d->c1;
     if ((d->c0 & 7) || (d->c1 & 7) || cin <= 0) return C2D_E_SHAPE;
     if (d->kpad & 63) return C2D_E_SHAPE;
-    const int ktot = d->ksize * d->ksize * cin;
+    const bool fold = d->up == 2;   // validated by c2d_conv2d_igemm (fold_check)
+    const int ktot = (fold ? 4 : d->ksize * d->ksize) * cin;
     if (d->kpad < ktot) return C2D_E_SHAPE;
     if ((d->cout & 3) || d->cout <= 0) return C2D_E_SHAPE;
     if (d->act == C2D_ACT_GEGLU && (d->cout & 31)) return C2D_E_SHAPE;
@@ -1532,6 +1652,11 @@ static int conv_run(const c2d_conv_desc* d, hipStream_t s, const DmaPlan* fixed)
     p.resid = (const f16*)d->resid; p.resid_ld = d->resid_ld;
     p.out = (f16*)d->out; p.out_ld = d->out_ld;
     p.M = d->n * d->oh * d->ow;
+    if (fold) {   // the GEMM of one phase: the low-res grid (IgemmParamsFold); the grid runs four of them
+        p.oh = d->h; p.ow = d->w;
+        p.M = d->n * d->h * d->w;
+    }
+    const long M_all = (long)d->n * d->oh * d->ow;   // output rows (fold: 4 p.M)
     p.gn_mom = (float*)d->gn_mom;   // c2d_conv2d_igemm checked gn_rows_for: a one-slice row-ring plan
     p.gn_cpg = d->gn_mom ? d->cout / d->gn_groups : 0;
     if (p.M <= 0) return C2D_OK;
@@ -1547,10 +1672,10 @@ static int conv_run(const c2d_conv_desc* d, hipStream_t s, const DmaPlan* fixed)
     p.cmajor = gemm_korder();
     const long t128 = (long)((p.M + 127) / 128) * ((d->cout + 127) / 128);
     if (dma) {
-        DmaPlan pl = fixed ? *fixed : plan_for(p.M, d->cout, d->kpad, d->act, pps_eligible(d), d->ksize, rr_eligible(d), panel_eligible(d));
+        DmaPlan pl = fixed ? *fixed : plan_for(M_all, d->cout, d->kpad, d->act, pps_eligible(d), plan_ksize(d), rr_eligible(d), panel_eligible(d));
         if (d->pro == C2D_PRO_LNFOLD) pl = {70, 1, d->kpad / 64};   // validated above: panel_eligible
         if (pl.split > 1) {
-            const size_t need = (size_t)pl.split * p.M * d->cout * sizeof(float);
+            const size_t need = (size_t)pl.split * M_all * d->cout * sizeof(float);
             if (d->ws && d->ws_bytes >= need && aligned16(d->ws)) {
                 p.ws = (float*)d->ws;
             } else {  // no / short workspace: same tile, one K slice
@@ -1558,7 +1683,9 @@ static int conv_run(const c2d_conv_desc* d, hipStream_t s, const DmaPlan* fixed)
                 pl.nkt = d->kpad / 64;
             }
         }
-        dispatch_dma(p, pl, d->ksize, d->cout, s);
+        dispatch_dma(p, pl, plan_ksize(d), d->cout, s);
+    } else if (fold) {
+        return C2D_E_SHAPE;
     } else if (t128 < 512) {
         p.gx = (d->cout + 63) / 64; p.gy = (p.M + 63) / 64;
         if (amode == AM_1X1) launch<64, 64, AM_1X1>(p, s);

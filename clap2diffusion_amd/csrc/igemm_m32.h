@@ -42,8 +42,11 @@ __device__ __forceinline__ int lds_sw(int row, int c) {
 // PRE: keep each A row's byte offset in both sources (a_off0 / a_off1, 2 x SA VGPRs) instead of
 // its pixel index (a_pix, SA VGPRs), so a piece's address costs a select and an or, not a 64-bit
 // multiply-add (igemm_sp.h issues its pieces inside the MFMA stream)
+// KS = 2: the folded upsample's 2x2 taps (ty, tx) from the window origin (i + a - 1, j + b - 1) of output
+// phase ph = 2 a + b (init's last argument); p.wt is the phase's own pack
 template <int BM, int BN, int BK, int NW, int KS, int SW = 0, bool PRE = false>
 struct M32Loader {
+    static constexpr int NT = KS * KS;   // taps
     static constexpr int RB = 2 * BK, RPP = 1024 / RB, CPR = BK / 8;
     static constexpr int NA = BM / RPP, NB = BN / RPP;
     static constexpr int SA = NA / NW;
@@ -67,19 +70,20 @@ struct M32Loader {
     // logical channel chunk this lane fetches so that the lane-linear image is swizzled (lds_sw)
     __device__ __forceinline__ int chunk_of(int row) const { return (lchunk ^ sw_of<BK, SW>(row)) * 8; }
 
-    __device__ __forceinline__ void init(const IgemmParams& p, int m0, int n0, int wave, int lane, int kb) {
+    __device__ __forceinline__ void init(const IgemmParams& p, int m0, int n0, int wave, int lane, int kb, int ph = 0) {
         lrow = lane / CPR;
         lchunk = lane % CPR;
         const int hw = p.oh * p.ow;
         two = p.c1 > 0;
-        pshift = KS == 3 ? p.w + 1 : 0;
+        pshift = KS >= 2 ? p.w + 1 : 0;
 #pragma unroll
         for (int i = 0; i < SA; ++i) {
             const int m = m0 + row_of(wave, i);
             const int mm = m < p.M ? m : 0;
             const int nn = mm / hw, r = mm - nn * hw;
             const int oy = r / p.ow, ox = r - oy * p.ow;
-            const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
+            int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
+            if constexpr (KS == 2) { iy0 = oy + (ph >> 1) - 1; ix0 = ox + (ph & 1) - 1; }
             unsigned mask = 0;
             if (m < p.M) {
 #pragma unroll
@@ -117,8 +121,8 @@ struct M32Loader {
         u_wt = uniform_ptr(p.wt);
         cbase = kb * BK;
         tap = 0;
-        if (KS == 3) {
-            if (p.cmajor) { tap = kb % 9; cbase = (kb / 9) * BK; }
+        if (KS >= 2) {
+            if (p.cmajor) { tap = kb % NT; cbase = (kb / NT) * BK; }
             else { tap = cbase / p.cin; cbase -= tap * p.cin; }
         }
     }
@@ -135,10 +139,10 @@ struct M32Loader {
     __device__ __forceinline__ Stage prep_at(const IgemmParams& p, int tap, int cbase) const {
         Stage st;
         const int k0 = tap * p.cin + cbase;              // packed weight column of this step
-        const int ky = tap / 3, kx = tap - (tap / 3) * 3;
+        const int ky = tap / (KS == 2 ? 2 : 3), kx = tap - ky * (KS == 2 ? 2 : 3);
         const bool use1 = two && cbase >= p.c0;
         st.cs = use1 ? p.c1 : p.c0;
-        const unsigned sterm = 2u * (unsigned)((KS == 3 ? (ky * p.w + kx) * st.cs : 0) + (use1 ? cbase - p.c0 : cbase));
+        const unsigned sterm = 2u * (unsigned)((KS >= 2 ? (ky * p.w + kx) * st.cs : 0) + (use1 ? cbase - p.c0 : cbase));
         const char* sb = use1 ? u_src1 : u_src0;
         const unsigned bias = 2u * (unsigned)(pshift * st.cs);
         const unsigned sbytes = use1 ? bytes1 : bytes0;
@@ -168,11 +172,11 @@ struct M32Loader {
         }
     }
     __device__ __forceinline__ void advance() {
-        if (KS == 3 && cbase_major) {                     // taps inner (C2D_TUNE_GEMM_KORDER)
-            if (++tap == 9) { tap = 0; cbase += BK; }
+        if (KS >= 2 && cbase_major) {                     // taps inner (C2D_TUNE_GEMM_KORDER)
+            if (++tap == NT) { tap = 0; cbase += BK; }
         } else {
             cbase += BK;
-            if (KS == 3 && cbase >= cin_) { cbase = 0; ++tap; }
+            if (KS >= 2 && cbase >= cin_) { cbase = 0; ++tap; }
         }
     }
 

@@ -41,8 +41,11 @@ namespace c2d {
 // accumulator registers of this tile do not fit the AGPR half the allocator grants at two
 // waves per SIMD: with the AGPR-form hint it split them and copied in the loop (40 % slower),
 // and inline-asm "+a" MFMAs computed wrong results (hazards invisible to the compiler).
+// KS = 2: the folded upsample (c2d_conv_desc::up = 2; IgemmParamsFold in igemm.hip)
 template <int TN, int KS, int PH>
-__global__ void __launch_bounds__(512) igemm_pp16_kernel(IgemmParams p) {
+__global__ void __launch_bounds__(512) igemm_pp16_kernel(IgemmParams pk) {
+    KernelParams<KS == 2> kp(pk);
+    auto& p = kp.p;
     constexpr int BK = 64, NW = 8, TMW = 8;
     constexpr int BM = 2 * TMW * 16, BN = 4 * TN * 16;
     constexpr int RB = 2 * BK, STAGE = (BM + BN) * RB;
@@ -64,13 +67,16 @@ __global__ void __launch_bounds__(512) igemm_pp16_kernel(IgemmParams p) {
     const int wr = wave >> 2, wc = wave & 3;
     const int bid = xcd_remap(blockIdx.x, p.gx * p.gy * p.ksplit);
     const int tile = bid / p.ksplit, slice = bid - tile * p.ksplit;
-    const int mt = tile / p.gx, nt = tile - mt * p.gx;
+    int mt = tile / p.gx;
+    const int nt = tile - mt * p.gx;
+    int ph = 0;
+    if constexpr (KS == 2) { mt = kp.set_phase(mt); ph = p.ph; }
     const int m0 = mt * BM, n0 = nt * BN;
     const int nk_all = p.kpad / BK;
     const int kb = slice * p.nkt, ke = min(nk_all, kb + p.nkt);
 
     Loader ld;
-    ld.init(p, m0, n0, wave, lane, kb);
+    ld.init(p, m0, n0, wave, lane, kb, ph);
     // fragment offsets: 16x16x32 operand = 16 rows (lane & 15) x 8 k (chunk lane >> 4) per k32
     const int fo0 = lds_sw<BK>(lane & 15, lane >> 4), fo1 = lds_sw<BK>(lane & 15, 4 + (lane >> 4));
     const int a_base = wr * TMW * 16 * RB, b_base = BM * RB + wc * TN * 16 * RB;
@@ -223,7 +229,7 @@ __global__ void __launch_bounds__(512) igemm_pp16_kernel(IgemmParams p) {
 
 template <int TN, int KS>
 static void launch_pp16(const IgemmParams& p, hipStream_t s) {
-    constexpr int PH = C2D_PP16_PH ? C2D_PP16_PH : ((KS == 1 || TN == 4) ? 2 : 4);
+    constexpr int PH = C2D_PP16_PH ? C2D_PP16_PH : ((KS == 1 || TN == 4) ? 2 : 4);   // KS = 2 as the 3x3
     constexpr int ring = 2 * (256 + 4 * TN * 16) * 128;
     constexpr int epi_wg = 64 * (4 * TN * 16 + 4) * 4, epi_wv = 8 * 32 * (TN * 16 + 4) * 4;   // epilogue images
     constexpr int epi = epi_wg > epi_wv ? epi_wg : epi_wv;
@@ -239,8 +245,11 @@ template <int TN>
 static void run_pp16(IgemmParams& p, int ksize, int cout, hipStream_t s) {
     constexpr int BM = 256, BN = 4 * TN * 16;
     p.gx = (cout + BN - 1) / BN;
-    p.gy = (p.M + BM - 1) / BM;
+    p.gy = (p.M + BM - 1) / BM * (ksize == 2 ? 4 : 1);   // ksize 2: the folded upsample, every phase its own row tiles
     if (ksize == 1) launch_pp16<TN, 1>(p, s);
+#if C2D_TUNE_UPFOLD
+    else if (ksize == 2) launch_pp16<TN, 2>(p, s);
+#endif
     else launch_pp16<TN, 3>(p, s);
 }
 

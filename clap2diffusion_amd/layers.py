@@ -62,6 +62,28 @@ class HConv2d(nn.Module):
         return ops.conv(x, self.weight, self.kpad, self.cout, ksize=self.ksize, stride=self.stride, bias=self.bias, **kw)
 
 
+class HUpConv2d(HConv2d):
+    """The 3x3 conv of an Upsample2D (nearest x2 before it).  Besides the 3x3 pack it keeps the conv folded
+    into the four 2x2 phase convs of the low-res input (ops.fold_upsample_weight, built from the fp32
+    checkpoint weight at load; not a checkpoint key) for the library's folded-upsample mode."""
+
+    def __init__(self, cin: int, cout: int):
+        super().__init__(cin, cout, 3)
+        self.kpad_fold = 4 * cin
+        self.register_buffer("weight_fold", torch.zeros(4, cout, self.kpad_fold, dtype=torch.float16), persistent=False)
+
+    @torch.no_grad()
+    def load(self, w: torch.Tensor, b: torch.Tensor | None) -> None:
+        super().load(w, b)
+        wf, kp = ops.fold_upsample_weight(w.float())
+        assert kp == self.kpad_fold
+        self.weight_fold.copy_(wf)
+
+    def forward_folded(self, x: torch.Tensor) -> torch.Tensor:
+        """x: the low-res [N, H, W, cin] -> [N, 2H, 2W, cout]."""
+        return ops.conv(x, self.weight_fold, self.kpad_fold, self.cout, ksize=3, bias=self.bias, up_fold=True)
+
+
 class HGroupNorm(nn.Module):
     """GroupNorm parameters; `stats(x)` returns the folded (scale, shift) tables
     consumed by the conv prologue (c2d_groupnorm_stats)."""

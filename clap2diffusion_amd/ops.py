@@ -68,6 +68,44 @@ def pack_linear_weight(w: torch.Tensor) -> tuple[torch.Tensor, int]:
     return wp.to(F16).contiguous(), kp
 
 
+# nearest x2 followed by a 3x3 (pad 1): output pixel (2i + a, 2j + b) reads only a 2x2 low-res neighbourhood;
+# _UPFOLD_TAPS[a][t] = the 3x3 taps along one axis that land on 2x2 tap t of phase a
+_UPFOLD_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))
+
+
+@torch.no_grad()
+def fold_upsample_weight(w: torch.Tensor, dtype: torch.dtype = F16) -> tuple[torch.Tensor, int]:
+    """Upsample2D's [cout, cin, 3, 3] weight -> the four 2x2 phase convs of the low-res image
+    (c2d_conv_desc::up = 2): [4][cout][kpad = 4 cin], phase 2a + b, K ordered (ty, tx, cin).  Tap (ty, tx) of
+    output (2i + a, 2j + b) reads low-res pixel (i + a - 1 + ty, j + b - 1 + tx).  Summed in w's dtype (the
+    fp32 checkpoint weights) and rounded to `dtype` once."""
+    cout, cin, kh, kw = w.shape
+    assert kh == 3 and kw == 3
+    out = w.new_zeros(4, cout, 2, 2, cin)
+    for a in range(2):
+        for b in range(2):
+            for ty in range(2):
+                for tx in range(2):
+                    acc = out[2 * a + b, :, ty, tx, :]
+                    for ky in _UPFOLD_TAPS[a][ty]:
+                        for kx in _UPFOLD_TAPS[b][tx]:
+                            acc += w[:, :, ky, kx]
+    return out.reshape(4, cout, 4 * cin).to(dtype).contiguous(), 4 * cin
+
+
+@functools.lru_cache(maxsize=None)
+def upfold_ok(n: int, h: int, w: int, cin: int, cout: int) -> bool:
+    """Does the library take this Upsample2D conv as a folded upsample (c2d_conv_desc::up = 2)?  Not with
+    cin % 64 != 0, nor a build without the mode: the caller then materialises the x2 tensor."""
+    import ctypes
+    from ._lib import ConvDesc, lib
+    d = ConvDesc()
+    d.c0, d.n, d.h, d.w, d.oh, d.ow, d.ksize, d.stride, d.up = cin, n, h, w, 2 * h, 2 * w, 3, 1, 2
+    d.cout, d.kpad, d.out_ld = cout, 4 * cin, cout
+    tid, ks = ctypes.c_int(), ctypes.c_int()
+    return lib().c2d_conv2d_igemm_plan(ctypes.byref(d), ctypes.byref(tid), ctypes.byref(ks)) == 0
+
+
 def geglu_interleave(w: torch.Tensor, b: torch.Tensor | None):
     """GEGLU proj [2I, in] (rows: h then g, diffusers chunk(2, -1)) -> rows in
     32-row blocks [h(16) | g(16)] so one MFMA column tile pair yields h*gelu(g)."""
@@ -85,7 +123,7 @@ def conv(x: torch.Tensor, weight: torch.Tensor, kpad: int, cout: int, *, ksize: 
          up: bool = False, x2: torch.Tensor | None = None, gn=None, gn_silu: bool = False, ln=None,
          silu_in: bool = False, act: str | None = None, temb: torch.Tensor | None = None,
          resid: torch.Tensor | None = None, out: torch.Tensor | None = None, padded: bool = False,
-         ln_fold=None, gn_moments: int = 0):
+         ln_fold=None, gn_moments: int = 0, up_fold: bool = False):
     """Implicit-GEMM conv / linear (c2d::conv2d_igemm).
 
     x: NHWC [N, H, W, C0] fp16 (or 2-D [M, C0] for a linear layer); padded: x is the
@@ -95,6 +133,8 @@ def conv(x: torch.Tensor, weight: torch.Tensor, kpad: int, cout: int, *, ksize: 
     (weight = W diag(gamma), bias = b + W beta; fold_layernorm builds them), panel GEMM shapes only.
     gn_moments = G > 0: also have the conv emit the GroupNorm moments of its output over G groups
     where the library can (c2d_conv2d_gn_rows); returns (out, GnMoments or None) instead of out.
+    up_fold: the folded upsample (c2d_conv_desc::up = 2): x is the low-res tensor, weight the phase pack of
+    fold_upsample_weight, the output [N, 2H, 2W, cout]; `up` keeps its meaning (the nearest-x2 view).
     """
     _require(x, "x")
     if x.dim() == 2:
@@ -109,8 +149,12 @@ def conv(x: torch.Tensor, weight: torch.Tensor, kpad: int, cout: int, *, ksize: 
     assert x.is_contiguous() and x.dtype == F16
     if x2 is not None:
         assert x2.is_contiguous() and x2.dtype == F16 and x2.shape[:-1] == x.shape[:-1]
+    if up_fold:
+        assert ksize == 3 and stride == 1 and not up and not padded and x2 is None and x.dim() == 4
+        assert gn is None and ln is None and not silu_in and act is None and temb is None and resid is None
+        assert not gn_moments and not ln_fold
     if ksize == 3:
-        vh, vw = (2 * h, 2 * w) if up else (h, w)
+        vh, vw = (2 * h, 2 * w) if up or up_fold else (h, w)
         oh, ow = (vh + 2 - 3) // stride + 1, (vw + 2 - 3) // stride + 1
     else:
         oh, ow = h, w
@@ -130,7 +174,8 @@ def conv(x: torch.Tensor, weight: torch.Tensor, kpad: int, cout: int, *, ksize: 
         if rows:
             mom = torch.empty((out.shape[0], oh * ow // rows, gn_moments, 2), device=x.device, dtype=torch.float32)
     C2D.conv2d_igemm(x, weight, kpad, cout, ksize, stride, up, x2, gs, gh, gn_silu, ls, lg, lb, silu_in, bias,
-                     C2D_ACT[act], temb, resid, out, bool(padded), float(ln_fold or 0.0), mom, int(gn_moments))
+                     C2D_ACT[act], temb, resid, out, bool(padded), float(ln_fold or 0.0), mom, int(gn_moments),
+                     bool(up_fold))
     if gn_moments:
         return out, (GnMoments(out, mom, rows, gn_moments) if mom is not None else None)
     return out

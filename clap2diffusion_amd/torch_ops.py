@@ -25,7 +25,7 @@ _CU = "cuda"
 
 def _conv_desc(x, weight, kpad, cout, ksize, stride, up, x2, gn_scale, gn_shift, gn_silu, ln_stats, ln_gamma,
                ln_beta, silu_in, bias, act, temb, resid, out, src_pad=False, lnf_eps=0.0, gn_mom=None,
-               gn_groups=0) -> ConvDesc:
+               gn_groups=0, up_fold=False) -> ConvDesc:
     if x.dim() == 2:
         n, h, w = 1, 1, x.shape[0]
         c0 = x.shape[1]
@@ -35,14 +35,14 @@ def _conv_desc(x, weight, kpad, cout, ksize, stride, up, x2, gn_scale, gn_shift,
             h, w = h - 2, w - 2
     c1 = x2.shape[-1] if x2 is not None else 0
     if ksize == 3:
-        vh, vw = (2 * h, 2 * w) if up else (h, w)
+        vh, vw = (2 * h, 2 * w) if up or up_fold else (h, w)
         oh, ow = (vh + 2 - 3) // stride + 1, (vw + 2 - 3) // stride + 1
     else:
         oh, ow = h, w
     d = ConvDesc()
     d.src0 = ptr(x); d.src1 = ptr(x2); d.c0 = c0; d.c1 = c1
     d.n, d.h, d.w, d.oh, d.ow = n, h, w, oh, ow
-    d.ksize, d.stride, d.up = ksize, stride, int(up)
+    d.ksize, d.stride, d.up = ksize, stride, (2 if up_fold else int(up))   # 2: the folded upsample
     d.weight = ptr(weight); d.cout = cout; d.kpad = kpad
     if lnf_eps > 0.0:   # LayerNorm folded into the panel GEMM (weight = W diag(gamma), bias = b + W beta)
         d.pro = C2D_PRO_LNFOLD; d.pro_eps = lnf_eps
@@ -77,14 +77,16 @@ def conv2d_igemm(x: Tensor, weight: Tensor, kpad: int, cout: int, ksize: int, st
                  ln_stats: Optional[Tensor], ln_gamma: Optional[Tensor], ln_beta: Optional[Tensor], silu_in: bool,
                  bias: Optional[Tensor], act: int, temb: Optional[Tensor], resid: Optional[Tensor],
                  out: Tensor, src_pad: bool = False, lnf_eps: float = 0.0, gn_mom: Optional[Tensor] = None,
-                 gn_groups: int = 0) -> None:
+                 gn_groups: int = 0, up_fold: bool = False) -> None:
     """c2d_conv2d_igemm (+ its split-K workspace, sized by c2d_conv2d_igemm_workspace_size).
     src_pad: x is the zero-bordered layout [n][h + 2][w + 2][c] (c2d_groupnorm_pad).
     lnf_eps > 0: a LayerNorm (that eps) folded into the GEMM (C2D_PRO_LNFOLD).
     gn_mom: fp32 [n][hw / rows][gn_groups][2], the output's GroupNorm moments written by the conv
-    (c2d_conv_desc::gn_mom; rows = c2d_conv2d_gn_rows)."""
+    (c2d_conv_desc::gn_mom; rows = c2d_conv2d_gn_rows).
+    up_fold: the folded upsample (c2d_conv_desc::up = 2): x low-res, weight the [4][cout][4 cin] phase pack, out
+    [n][2h][2w][cout]; `up` stays the nearest-x2 view of the register-staged 3x3."""
     d = _conv_desc(x, weight, kpad, cout, ksize, stride, up, x2, gn_scale, gn_shift, gn_silu, ln_stats, ln_gamma,
-                   ln_beta, silu_in, bias, act, temb, resid, out, src_pad, lnf_eps, gn_mom, gn_groups)
+                   ln_beta, silu_in, bias, act, temb, resid, out, src_pad, lnf_eps, gn_mom, gn_groups, up_fold)
     wsb = lib().c2d_conv2d_igemm_workspace_size(ctypes.byref(d))
     if wsb:
         ws = torch.empty(wsb // 4, device=x.device, dtype=torch.float32)
@@ -98,7 +100,7 @@ def conv2d_igemm(x: Tensor, weight: Tensor, kpad: int, cout: int, ksize: int, st
 
 @conv2d_igemm.register_fake
 def _(x, weight, kpad, cout, ksize, stride, up, x2, gn_scale, gn_shift, gn_silu, ln_stats, ln_gamma, ln_beta,
-      silu_in, bias, act, temb, resid, out, src_pad=False, lnf_eps=0.0, gn_mom=None, gn_groups=0):
+      silu_in, bias, act, temb, resid, out, src_pad=False, lnf_eps=0.0, gn_mom=None, gn_groups=0, up_fold=False):
     return None
 
 

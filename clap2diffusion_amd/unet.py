@@ -33,8 +33,8 @@ blocks, GN+SiLU+conv_out.  Fusions on the HIP path:
   taps of a 3x3 conv / every N-tile of a GEMM, which is VALU-bound on CDNA4 -- the panel GEMM
   escapes that because it normalises each A row once, in LDS, for all of its output columns.
   Up/Downsample   stride 2 folded into the conv addressing; the nearest x2 upsample
-                  materialised by c2d_upsample_nearest2x (one HBM pass) so the 3x3 conv
-                  stays on the LDS-DMA path (Upsample2D below).
+                  folded into the conv's weights: four 2x2 phase convs of the low-res
+                  tensor in one launch (c2d_conv_desc::up = 2, Upsample2D below).
   CFG pair        conv_in, the first resnet and the first transformer up to its
                   cross-attention run once per latent (cfg_pair=True); each producer
                   writes the first half of a 2N buffer and one device copy fills the
@@ -48,7 +48,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .layers import HConv2d, HGroupNorm, HLayerNorm, HLinear
+from .layers import HConv2d, HGroupNorm, HLayerNorm, HLinear, HUpConv2d
 from .processor import AttnProcessor, AudioAttnProcessor
 from .weights import SD15_UNET
 
@@ -398,11 +398,17 @@ class Downsample2D(nn.Module):
 
 
 class Upsample2D(nn.Module):
+    """Nearest x2 + 3x3 conv as four folded 2x2 phase convs of the low-res tensor (HUpConv2d: no upsampled
+    tensor, 4/9 of the MACs); shapes the library does not take that way materialise the x2 tensor."""
+
     def __init__(self, c):
         super().__init__()
-        self.conv = HConv2d(c, c, 3)
+        self.conv = HUpConv2d(c, c)
 
     def forward(self, x):
+        n, h, w, c = x.shape
+        if ops.upfold_ok(n, h, w, c, self.conv.cout):
+            return self.conv.forward_folded(x)
         # materialised x2 (one HBM pass) keeps the conv on the LDS-DMA path
         return self.conv(ops.upsample_nearest2x(x))
 

@@ -63,7 +63,30 @@ extern "C" {
  * zero filled).  Input channels may come from two sources (skip concat:
  * channels [0,c0) from src0, [c0,c0+c1) from src1) without materialising the
  * concatenation.  ksize 1 = linear / 1x1 conv; ksize 3 = 3x3 conv with pad 1,
- * stride 1 or 2, optionally reading a nearest-x2-upsampled view of the input.
+ * stride 1 or 2, optionally reading a nearest-x2-upsampled view of the input (up = 1), or
+ * folded with that upsample into four 2x2 convs of the low-res input (up = 2, below).
+ *
+ * Folded upsample (up = 2): the 3x3 conv (pad 1, stride 1) of the nearest-x2 upsampled input, computed
+ * without the upsampled tensor and with 4/9 of its multiply-adds.  Output pixel (2i + a, 2j + b),
+ * a, b in {0, 1}, reads only a 2x2 low-res neighbourhood, so the layer is four 2x2 convs, one per
+ * output phase (a, b), run as one launch:
+ *   out[n, 2i + a, 2j + b, :] = bias + sum_{ty, tx in {0,1}} Wf[2a + b][:, ty, tx, :] . x[n, i + a - 1 + ty, j + b - 1 + tx, :]
+ * with x read as zero outside [0, h) x [0, w) (exactly the 3x3's padding of the upsampled image).
+ *   weight  the phase pack fp16 [4][cout][kpad], phase index 2a + b, K ordered (ty, tx, cin),
+ *           kpad = 4 * c0; Wf[a, b][co][ty][tx][ci] = sum of W[co][ci][ky][kx] over ky in S(a, ty),
+ *           kx in S(b, tx), S(0,0) = {0}, S(0,1) = {1, 2}, S(1,0) = {0, 1}, S(1,1) = {2}: summed in
+ *           fp32 from the fp32 weights and rounded to fp16 once (the weights are constant: at load).
+ *   shape   ksize = 3, stride = 1, one source (c1 = 0, src1 NULL), c0 % 64 == 0, oh = 2h, ow = 2w,
+ *           n * h * w < 2^24, cout % 4 == 0, the 32-bit buffer offsets of the LDS-DMA kernels; anything
+ *           else C2D_E_SHAPE.  Bias allowed.
+ *   not taken (C2D_E_ARG): a prologue (pro != C2D_PRO_NONE), src_pad, an activation, temb, resid.
+ *   gn_mom  C2D_E_SHAPE: c2d_conv2d_gn_rows is 0 for the mode (its consumer in the UNet is the
+ *           [h; skip] norm, which runs its own statistics pass).
+ * c2d_conv2d_igemm_plan / c2d_conv2d_igemm_workspace_size answer for it as the launch behaves (the plan
+ * query returns the same error codes; the workspace query 0).  It runs on the ping-pong tiles 40 / 41 and
+ * the 16x16x32 LDS-DMA tiles (1, 2, 3, 7, 8, 9, 80, 81), split-K included; never on the row-ring tiles,
+ * the panel GEMM, tile 50 or the 32x32 tiles -- a forced plan naming one of those is ignored.
+ * A library built with -DC2D_TUNE_UPFOLD=0 (A/B only) answers C2D_E_SHAPE to up = 2.
  *
  * Replaces (diffusers 0.23.1): ResnetBlock2D.norm1/2+SiLU+conv1/conv2+temb add+
  * shortcut, Downsample2D/Upsample2D convs, conv_in/conv_out, Transformer2DModel
@@ -81,10 +104,11 @@ typedef struct c2d_conv_desc {
     int oh, ow;              /* output spatial size                                       */
     int ksize;               /* 1 or 3                                                    */
     int stride;              /* 1 or 2 (3x3 only)                                         */
-    int up;                  /* 1: conv reads nearest-x2 upsampled input (3x3, stride 1)  */
-    const void* weight;      /* fp16 [cout][kpad]                                         */
+    int up;                  /* 1: conv reads nearest-x2 upsampled input (3x3, stride 1);
+                                2: folded upsample, weight = the [4][cout][4 c0] phase pack (above) */
+    const void* weight;      /* fp16 [cout][kpad]  (up = 2: [4][cout][kpad])              */
     int cout;                /* output columns (packed rows; GEGLU: 2x the output width)  */
-    int kpad;                /* packed K, multiple of 64, >= ksize*ksize*(c0+c1)          */
+    int kpad;                /* packed K, multiple of 64, >= ksize*ksize*(c0+c1); up = 2: 4*c0 */
     int pro;                 /* C2D_PRO_*                                                 */
     int pro_silu;            /* GN prologue: apply SiLU after the affine                  */
     const float* pro_a;      /* GN: scale [n][c0+c1]   LN: (mean,rstd) [m][2]             */
