@@ -16,6 +16,7 @@ import torch  # noqa: F401  (must be loaded first: the library binds to torch's 
 LIB_PATH = Path(os.environ.get("C2D_LIB") or Path(__file__).resolve().parent / "libc2d_hip.so")  # C2D_LIB: A/B builds
 
 C2D_PRO_NONE, C2D_PRO_GN, C2D_PRO_LN, C2D_PRO_SILU, C2D_PRO_LNFOLD = 0, 1, 2, 3, 4
+C2D_PAD_SAME, C2D_PAD_AFTER = 0, 1
 C2D_ACT = {None: 0, "none": 0, "geglu": 1, "gelu": 2, "relu": 3, "silu": 4, "quick_gelu": 5}
 ERRORS = {-1: "C2D_E_ARG", -2: "C2D_E_SHAPE", -3: "C2D_E_ALIGN", -4: "C2D_E_HIP"}
 
@@ -25,6 +26,7 @@ EXPORTS = [
     "c2d_layernorm", "c2d_attention_fwd", "c2d_attention_fwd_bias", "c2d_attention_fwd_mask", "c2d_window_attention", "c2d_htsat_mel_patches",
     "c2d_patch_merge_gather", "c2d_row_mean", "c2d_l2_normalize", "c2d_softmax_rows", "c2d_clap_log_mel", "c2d_attention_small", "c2d_pack_weights", "c2d_timestep_embedding",
     "c2d_cfg_ddim_step", "c2d_latent_to_nhwc", "c2d_upsample_nearest2x", "c2d_add", "c2d_last_hip_error", "c2d_version",
+    "c2d_image_to_nhwc", "c2d_vae_posterior_noise",
 ]
 
 
@@ -40,6 +42,7 @@ class ConvDesc(ctypes.Structure):
         ("out", c_void_p), ("out_ld", c_int), ("ws", c_void_p), ("ws_bytes", c_size_t),
         ("src_pad", c_int), ("pro_eps", c_float),
         ("gn_mom", c_void_p), ("gn_groups", c_int),   # r6: producer-emitted GroupNorm moments
+        ("pad_mode", c_int),                          # r7: C2D_PAD_AFTER = the VAE encoder's pad-after downsample
     ]
 
 
@@ -89,6 +92,8 @@ def lib() -> ctypes.CDLL:
         "c2d_cfg_ddim_step": ([vp, vp, i, i, i, f, vp, vp, i, vp], i),
         "c2d_latent_to_nhwc": ([vp, i, i, i, i, i, vp, vp], i),
         "c2d_upsample_nearest2x": ([vp, i, i, i, i, vp, vp], i),
+        "c2d_image_to_nhwc": ([vp, i, i, vp, vp], i),
+        "c2d_vae_posterior_noise": ([vp, i, vp, vp, vp, vp, i, i, f, vp, vp], i),
         "c2d_add": ([vp, vp, vp, sz, vp], i),
         "c2d_last_hip_error": ([], i),
         "c2d_version": ([], ctypes.c_char_p),

@@ -203,11 +203,48 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, int cout, int c
     out[i] = (f16)v;
 }
 
+// uint8 NHWC [n][hw][3] -> fp16 NHWC [n][hw][8], (u / 127.5 - 1) in channels 0..2, zeros above: one pixel per
+// thread, one 16-B store (the VAE encoder's conv_in reads 8-channel pixels)
+__global__ void image_to_nhwc_kernel(const uint8_t* __restrict__ img, size_t npix, f16x8* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    f16x8 v;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v[c] = (f16)0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = (f16)((float)img[i * 3 + c] / 127.5f - 1.0f);
+    out[i] = v;
+}
+
+// DiagonalGaussianDistribution.sample (or .mode) * scaling, NHWC fp16 moments -> NCHW fp32 latents, and
+// DDIMScheduler.add_noise at the step the device counter names: one thread per (image, channel, pixel)
+__global__ void vae_posterior_noise_kernel(const f16* __restrict__ mom, int ld, const float* __restrict__ eps,
+                                           const float* __restrict__ noise, const float* __restrict__ coef,
+                                           const int* __restrict__ step_index, int n, int hw, float scaling,
+                                           float* __restrict__ x) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n * 4 * hw) return;
+    const int p = (int)(i % hw), ch = (int)((i / hw) & 3);
+    const size_t bi = i / ((size_t)4 * hw);
+    const f16* row = mom + (bi * hw + p) * ld;
+    float z = (float)row[ch];
+    if (eps) {
+        const float lv = fminf(fmaxf((float)row[4 + ch], -30.0f), 20.0f);
+        z += expf(0.5f * lv) * eps[i];
+    }
+    z *= scaling;
+    if (noise) {
+        const float a = coef[2 * (*step_index)];
+        z = sqrtf(a) * z + sqrtf(1.0f - a) * noise[i];
+    }
+    x[i] = z;
+}
+
 }  // namespace c2d
 
 using namespace c2d;
 
-extern "C" const char* c2d_version(void) { return "c2d_hip gfx950 r6"; }
+extern "C" const char* c2d_version(void) { return "c2d_hip gfx950 r7"; }
 
 extern "C" int c2d_timestep_embedding(const float* t_table, const int* step_index, int n, int dim, void* out,
                                       void* stream) {
@@ -228,6 +265,28 @@ extern "C" int c2d_cfg_ddim_step(const void* eps, float* x, int b, int c, int hw
     hipLaunchKernelGGL(cfg_ddim_kernel, dim3((tot + 255) / 256), dim3(256), 0, s, (const f16*)eps, x, b, c, hw,
                        guidance, coef, step_index);
     if (advance) hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, step_index);
+    return check_launch();
+}
+
+extern "C" int c2d_image_to_nhwc(const uint8_t* img, int n, int hw, void* out, void* stream) {
+    if (!img || !out) return C2D_E_ARG;
+    if (n <= 0 || hw <= 0) return C2D_E_SHAPE;
+    if (!aligned16(out)) return C2D_E_ALIGN;
+    const size_t npix = (size_t)n * hw;
+    hipLaunchKernelGGL(image_to_nhwc_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       img, npix, (f16x8*)out);
+    return check_launch();
+}
+
+extern "C" int c2d_vae_posterior_noise(const void* moments, int ld, const float* eps, const float* noise,
+                                       const float* coef, const int* step_index, int n, int hw, float scaling,
+                                       float* x, void* stream) {
+    if (!moments || !x || (noise && (!coef || !step_index))) return C2D_E_ARG;
+    if (n <= 0 || hw <= 0 || ld < 8) return C2D_E_SHAPE;
+    if (((uintptr_t)moments & 1) || ((uintptr_t)x & 3)) return C2D_E_ALIGN;
+    const size_t tot = (size_t)n * 4 * hw;
+    hipLaunchKernelGGL(vae_posterior_noise_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, (const f16*)moments, ld, eps, noise, coef, step_index, n, hw, scaling, x);
     return check_launch();
 }
 

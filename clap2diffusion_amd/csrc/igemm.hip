@@ -1489,9 +1489,25 @@ static int fold_check(const c2d_conv_desc* d) {
     return C2D_OK;
 }
 
+// c2d_conv_desc::pad_mode: C2D_PAD_AFTER is the AutoencoderKL encoder's downsample, F.pad(x, (0, 1, 0, 1)) then a
+// 3x3 stride-2 conv with padding 0: the window origin is (2 oy, 2 ox) (IgemmParams::pad = 0) and input row h /
+// column w read as zero through the same upper-bound tap masks as the right / bottom halo of a pad-1 conv.  Every
+// kernel a 3x3 without a zero-bordered source can plan to takes its window origin from p.pad (igemm_kernel,
+// igemm_dma_kernel, M32Loader: tiles 1-3, 7-9, 80 / 81, 25 / 28 / 29, 40 / 41; the split-K combine never sees the
+// window); the row-ring tiles need src_pad and the panel GEMM / tile 50 a 1x1, so plan_for drops a forced plan
+// naming one of them.  C2D_OK or the code c2d_conv2d_igemm returns
+static int pad_mode_check(const c2d_conv_desc* d) {
+    if (d->pad_mode == C2D_PAD_SAME) return C2D_OK;
+    if (d->pad_mode != C2D_PAD_AFTER) return C2D_E_ARG;
+    if (d->ksize != 3 || d->stride != 2 || d->up || d->src_pad) return C2D_E_SHAPE;
+    if (d->h <= 0 || d->w <= 0 || (d->h & 1) || (d->w & 1) || d->oh != d->h / 2 || d->ow != d->w / 2) return C2D_E_SHAPE;
+    return C2D_OK;
+}
+
 extern "C" size_t c2d_conv2d_igemm_workspace_size(const c2d_conv_desc* d) {
     if (!d || d->ksize < 1 || d->oh <= 0 || d->ow <= 0 || d->n <= 0 || d->cout <= 0 || d->kpad < 64) return 0;
     if (d->up == 2 && fold_check(d) != C2D_OK) return 0;
+    if (pad_mode_check(d) != C2D_OK) return 0;
     if (!dma_eligible(d)) return 0;
     if (d->pro == C2D_PRO_LNFOLD) return 0;   // the panel GEMM, one slice
     const long M = (long)d->n * d->oh * d->ow;
@@ -1511,7 +1527,7 @@ static bool gn_split_ok(int ks) {   // the slice counts splitk_reduce_gn_kernel 
 }
 
 static int gn_rows_for(const c2d_conv_desc* d) {
-    if (!d || d->gn_groups <= 0 || d->cout % d->gn_groups || d->up == 2) return 0;
+    if (!d || d->gn_groups <= 0 || d->cout % d->gn_groups || d->up == 2 || pad_mode_check(d) != C2D_OK) return 0;
     const int cpg = d->cout / d->gn_groups;
     if (320 % cpg || d->cout % 320 || d->act != C2D_ACT_NONE) return 0;
     if ((d->out_ld & 7) || (d->resid && (d->resid_ld & 7)) || (d->temb && (d->temb_ld & 7)) || d->out_ld < d->cout) return 0;
@@ -1548,6 +1564,7 @@ extern "C" int c2d_conv2d_igemm_plan(const c2d_conv_desc* d, int* tile_id, int* 
         const int rc = fold_check(d);
         if (rc != C2D_OK) return rc;
     }
+    if (const int rc = pad_mode_check(d)) return rc;
     if (d->pro == C2D_PRO_LNFOLD) {   // the panel GEMM or nothing (c2d_conv2d_igemm rejects the rest the same way)
         if (!panel_eligible(d)) return C2D_E_SHAPE;
         *tile_id = 70;
@@ -1580,6 +1597,7 @@ extern "C" int c2d_conv2d_igemm(const c2d_conv_desc* d, void* stream) {
         const int rc = fold_check(d);
         if (rc != C2D_OK) return rc;
     }
+    if (const int rc = pad_mode_check(d)) return rc;
     if (d->gn_mom && gn_rows_for(d) == 0) return C2D_E_SHAPE;   // moments requested of a plan that cannot emit them
     if (d->gn_mom && ((uintptr_t)d->gn_mom & 7)) return C2D_E_ALIGN;
     if (d->n >= 2 && d->ksize >= 1 && d->oh > 0 && d->ow > 0 && d->cout > 0 && d->kpad >= 64 && dma_eligible(d)) {
@@ -1639,6 +1657,8 @@ static int conv_run(const c2d_conv_desc* d, hipStream_t s, const DmaPlan* fixed)
     p.vh = d->up ? 2 * d->h : d->h; p.vw = d->up ? 2 * d->w : d->w;
     if (d->src_pad) {   // a valid 3x3 over the padded image: every kernel's addressing as is, no halo
         p.h = d->h + 2; p.w = d->w + 2; p.vh = p.h; p.vw = p.w; p.pad = 0;
+    } else if (d->pad_mode == C2D_PAD_AFTER) {   // validated by c2d_conv2d_igemm (pad_mode_check): oh = h / 2, ow = w / 2
+        p.pad = 0;
     } else if (d->ksize == 3) {
         int eh = (p.vh + 2 - 3) / d->stride + 1, ew = (p.vw + 2 - 3) / d->stride + 1;
         if (eh != d->oh || ew != d->ow) return C2D_E_SHAPE;

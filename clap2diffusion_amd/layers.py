@@ -40,11 +40,14 @@ class HLinear(nn.Module):
 
 
 class HConv2d(nn.Module):
-    """NHWC conv (ksize 1 or 3, pad = ksize // 2) on the implicit-GEMM kernel."""
+    """NHWC conv (ksize 1 or 3, pad = ksize // 2) on the implicit-GEMM kernel.  pad_after: the AutoencoderKL
+    encoder's downsample instead (3x3, stride 2, one zero row / column after the image only, padding 0)."""
 
-    def __init__(self, cin: int, cout: int, ksize: int, stride: int = 1, cin_pad: int | None = None):
+    def __init__(self, cin: int, cout: int, ksize: int, stride: int = 1, cin_pad: int | None = None,
+                 pad_after: bool = False):
         super().__init__()
-        self.cin, self.cout, self.ksize, self.stride = cin, cout, ksize, stride
+        assert not pad_after or (ksize == 3 and stride == 2)
+        self.cin, self.cout, self.ksize, self.stride, self.pad_after = cin, cout, ksize, stride, pad_after
         self.cin_pad = cin_pad or cin
         self.kpad = ops.kpad_of(ksize * ksize * self.cin_pad)
         self.register_buffer("weight", torch.zeros(cout, self.kpad, dtype=torch.float16))
@@ -59,6 +62,8 @@ class HConv2d(nn.Module):
             self.bias.copy_(b.float())
 
     def forward(self, x: torch.Tensor, **kw) -> torch.Tensor:
+        if self.pad_after:
+            kw["pad_after"] = True
         return ops.conv(x, self.weight, self.kpad, self.cout, ksize=self.ksize, stride=self.stride, bias=self.bias, **kw)
 
 

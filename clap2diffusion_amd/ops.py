@@ -123,7 +123,7 @@ def conv(x: torch.Tensor, weight: torch.Tensor, kpad: int, cout: int, *, ksize: 
          up: bool = False, x2: torch.Tensor | None = None, gn=None, gn_silu: bool = False, ln=None,
          silu_in: bool = False, act: str | None = None, temb: torch.Tensor | None = None,
          resid: torch.Tensor | None = None, out: torch.Tensor | None = None, padded: bool = False,
-         ln_fold=None, gn_moments: int = 0, up_fold: bool = False):
+         ln_fold=None, gn_moments: int = 0, up_fold: bool = False, pad_after: bool = False):
     """Implicit-GEMM conv / linear (c2d::conv2d_igemm).
 
     x: NHWC [N, H, W, C0] fp16 (or 2-D [M, C0] for a linear layer); padded: x is the
@@ -135,6 +135,8 @@ def conv(x: torch.Tensor, weight: torch.Tensor, kpad: int, cout: int, *, ksize: 
     where the library can (c2d_conv2d_gn_rows); returns (out, GnMoments or None) instead of out.
     up_fold: the folded upsample (c2d_conv_desc::up = 2): x is the low-res tensor, weight the phase pack of
     fold_upsample_weight, the output [N, 2H, 2W, cout]; `up` keeps its meaning (the nearest-x2 view).
+    pad_after: the AutoencoderKL encoder's downsample (c2d_conv_desc::pad_mode = C2D_PAD_AFTER): 3x3, stride 2,
+    F.pad(x, (0, 1, 0, 1)) then padding 0, without the padded tensor; H and W even, output [N, H/2, W/2, cout].
     """
     _require(x, "x")
     if x.dim() == 2:
@@ -153,6 +155,9 @@ def conv(x: torch.Tensor, weight: torch.Tensor, kpad: int, cout: int, *, ksize: 
         assert ksize == 3 and stride == 1 and not up and not padded and x2 is None and x.dim() == 4
         assert gn is None and ln is None and not silu_in and act is None and temb is None and resid is None
         assert not gn_moments and not ln_fold
+    if pad_after:
+        assert ksize == 3 and stride == 2 and not up and not up_fold and not padded and x.dim() == 4
+        assert h % 2 == 0 and w % 2 == 0, "pad-after downsample: even H and W"
     if ksize == 3:
         vh, vw = (2 * h, 2 * w) if up or up_fold else (h, w)
         oh, ow = (vh + 2 - 3) // stride + 1, (vw + 2 - 3) // stride + 1
@@ -168,14 +173,14 @@ def conv(x: torch.Tensor, weight: torch.Tensor, kpad: int, cout: int, *, ksize: 
     gs, gh = gn if gn is not None else (None, None)
     ls, lg, lb = ln if ln is not None else (None, None, None)
     mom, rows = None, 0
-    if gn_moments and x.dim() == 4 and act is None and not up and out.is_contiguous():
+    if gn_moments and x.dim() == 4 and act is None and not up and not pad_after and out.is_contiguous():
         rows = gn_moment_rows(out.shape[0], oh, ow, x.shape[-1], cout, ksize, stride, bool(padded), resid is not None,
                               temb is not None, gn_moments, x2.shape[-1] if x2 is not None else 0)
         if rows:
             mom = torch.empty((out.shape[0], oh * ow // rows, gn_moments, 2), device=x.device, dtype=torch.float32)
     C2D.conv2d_igemm(x, weight, kpad, cout, ksize, stride, up, x2, gs, gh, gn_silu, ls, lg, lb, silu_in, bias,
                      C2D_ACT[act], temb, resid, out, bool(padded), float(ln_fold or 0.0), mom, int(gn_moments),
-                     bool(up_fold))
+                     bool(up_fold), bool(pad_after))
     if gn_moments:
         return out, (GnMoments(out, mom, rows, gn_moments) if mom is not None else None)
     return out
@@ -492,6 +497,35 @@ def latent_to_nhwc(x: torch.Tensor, cpad: int, dup: bool) -> torch.Tensor:
     b, c, hgt, wid = x.shape
     out = torch.empty(((2 if dup else 1) * b, hgt, wid, cpad), device=x.device, dtype=F16)
     C2D.latent_to_nhwc(x, cpad, bool(dup), out)
+    return out
+
+
+def image_to_nhwc(img: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """uint8 NHWC [N, H, W, 3] -> fp16 NHWC [N, H, W, 8] in [-1, 1], channels 3..7 zero (c2d::image_to_nhwc)."""
+    _require(img, "img")
+    assert img.dtype == torch.uint8 and img.dim() == 4 and img.shape[-1] == 3 and img.is_contiguous()
+    if out is None:
+        out = torch.empty((*img.shape[:-1], 8), device=img.device, dtype=F16)
+    C2D.image_to_nhwc(img, out)
+    return out
+
+
+def vae_posterior_noise(moments: torch.Tensor, out: torch.Tensor, scaling: float, eps: torch.Tensor | None = None,
+                        noise: torch.Tensor | None = None, coef: torch.Tensor | None = None,
+                        step_index: torch.Tensor | None = None) -> torch.Tensor:
+    """moments fp16 [N * h * w, >= 8] (mean | log-variance) -> out fp32 [N, 4, h, w] (c2d::vae_posterior_noise):
+    z = (mean + std * eps) * scaling (eps None: the mode); with noise, DDIMScheduler.add_noise at the alpha
+    coef[2 * step_index] read on the device."""
+    _require(moments, "moments")
+    assert moments.dim() == 2 and moments.dtype == F16 and moments.stride(1) == 1 and moments.shape[1] >= 8
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and out.shape[1] == 4
+    assert moments.shape[0] == out.shape[0] * out.shape[2] * out.shape[3]
+    for t in (eps, noise):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.shape == out.shape and t.is_cuda)
+    if noise is not None:
+        assert coef is not None and step_index is not None and coef.dtype == torch.float32
+        assert step_index.dtype == torch.int32
+    C2D.vae_posterior_noise(moments, eps, noise, coef, step_index, float(scaling), out)
     return out
 
 

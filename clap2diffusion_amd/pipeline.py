@@ -36,7 +36,8 @@ from .sampler import GraphDenoiser
 from .scheduler import DDIMScheduler
 from .text_encoder import TextEncoder, make_tokenizer
 from .unet import UNet2DConditionModel
-from .vae import VAEDecoder
+from .vae import SCALING, VAEDecoder, VAEEncoder
+from . import ops
 
 SR = 48000
 
@@ -59,6 +60,17 @@ def initial_latents(seeds: list[int], h: int, w: int, device=None) -> torch.Tens
     identical latents on any number of GPUs."""
     lat = [torch.randn(4, h, w, generator=torch.Generator().manual_seed(int(s))) for s in seeds]
     return torch.stack(lat).to(device)
+
+
+def initial_latents_and_eps(seeds: list[int], h: int, w: int, device=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """img2img noise: each sample's generator draws the initial noise (the same tensor initial_latents gives)
+    and, right after it, the posterior noise of the VAE encoder's sample."""
+    lat, eps = [], []
+    for s in seeds:
+        g = torch.Generator().manual_seed(int(s))
+        lat.append(torch.randn(4, h, w, generator=g))
+        eps.append(torch.randn(4, h, w, generator=g))
+    return torch.stack(lat).to(device), torch.stack(eps).to(device)
 
 
 _WAVE_PCM, _WAVE_FLOAT, _WAVE_EXTENSIBLE = 1, 3, 0xFFFE
@@ -185,6 +197,7 @@ class AudioToImageInference:
         self._denoisers = {}
         self._batch_graphs = {}
         self.last_denoiser = None
+        self._vae_encoder = None   # built on the first init image: text-to-image allocates nothing for it
 
     # ------------------------------------------------------------ models
     def _log(self, *a):
@@ -270,27 +283,90 @@ class AudioToImageInference:
     def apply_normalization(self, audio_tokens, target_norm=60.0):
         return normalize_tokens(audio_tokens, target_norm)
 
-    def _request_latents(self, n: int, seed) -> torch.Tensor:
+    # ------------------------------------------------------------ img2img
+    @property
+    def vae_encoder(self) -> VAEEncoder:
+        """The AutoencoderKL encoder, built and loaded on first use (the SD1.5 folder's vae/ file when one was
+        given, else the seeded recipe)."""
+        if self._vae_encoder is None:
+            enc = VAEEncoder().to(self.device)
+            enc.load_diffusers_state_dict(W.load_sd15_vae_encoder(self.sd_model_path) if self.sd_model_path
+                                          else W.synth_vae_encoder(self.seed))
+            self._vae_encoder = enc
+        return self._vae_encoder
+
+    def prepare_images(self, images, n: int | None = None) -> torch.Tensor:
+        """PIL image(s), path(s) or a uint8 tensor [B, H, W, 3] -> uint8 [B, H, W, 3] on the device at the
+        pipeline's size: converted to RGB and resized on the host (bicubic) where the size differs.  One
+        image given for n requests is repeated."""
+        if isinstance(images, torch.Tensor):
+            if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
+                raise ValueError(f"init images as a tensor must be uint8 [B, H, W, 3], got {images.dtype} "
+                                 f"{tuple(images.shape)}")
+            if tuple(images.shape[1:3]) == (self.height, self.width):
+                out = images.to(self.device).contiguous()
+            else:
+                images = list(images.cpu().numpy())
+        if not isinstance(images, torch.Tensor):
+            from PIL import Image
+            arr = []
+            for im in (list(images) if isinstance(images, (list, tuple)) else [images]):
+                if isinstance(im, (str, os.PathLike)):
+                    im = Image.open(im)
+                elif isinstance(im, np.ndarray):
+                    im = Image.fromarray(im)
+                im = im.convert("RGB")
+                if im.size != (self.width, self.height):
+                    im = im.resize((self.width, self.height), Image.BICUBIC)
+                arr.append(np.asarray(im, dtype=np.uint8))
+            out = torch.from_numpy(np.stack(arr)).to(self.device)
+        if n is not None and out.shape[0] != n:
+            if out.shape[0] != 1:
+                raise ValueError(f"{out.shape[0]} init images for {n} requests")
+            out = out.expand(n, -1, -1, -1).contiguous()
+        return out
+
+    @torch.no_grad()
+    def encode_image(self, images, eps: torch.Tensor | None = None) -> torch.Tensor:
+        """Image(s) (prepare_images forms) -> scaled latents fp32 [B, 4, H/8, W/8]; eps None = the posterior mode."""
+        return self.vae_encoder.encode(self.prepare_images(images), eps)
+
+    def _request_latents(self, n: int, seed, with_eps: bool = False):
         """Initial latents of n requests as the reference's generate() seeds them
         (scripts/inference.py:113-116: torch.manual_seed(seed) / np.random.seed(seed) when a seed
         is given, the RNG left as it is otherwise): each request draws [1, 4, h/8, w/8] from the
         global CPU generator right after its (re-)seeding, so a given seed always yields
-        initial_latents([seed]) and seed=None draws fresh noise every call."""
+        initial_latents([seed]) and seed=None draws fresh noise every call.  with_eps (img2img with a sampled
+        posterior): each request draws its posterior noise right after its initial noise, so a seed fixes
+        both; returns (latents, eps)."""
         h, w = self.height // 8, self.width // 8
-        lat = []
+        lat, eps = [], []
         for _ in range(n):
             if seed is not None:
                 torch.manual_seed(seed)
                 np.random.seed(seed)
             lat.append(torch.randn(1, 4, h, w))
+            if with_eps:
+                eps.append(torch.randn(1, 4, h, w))
+        if with_eps:
+            return torch.cat(lat).to(self.device), torch.cat(eps).to(self.device)
         return torch.cat(lat).to(self.device)
 
     @torch.no_grad()
     def generate(self, audio_path, text_prompt="", num_inference_steps=50, guidance_scale=7.5, seed=None,
-                 use_hierarchical=True):
+                 use_hierarchical=True, init_image=None, strength=0.8, sample_posterior=True):
+        """init_image (a PIL image, a path or a uint8 tensor [1, H, W, 3]): audio-guided image-to-image, the
+        schedule entered at DDIMScheduler.img2img_start(steps, strength) from the encoded image plus scheduled
+        noise; sample_posterior=False takes the VAE posterior's mode instead of a sample."""
         audio = self.load_audio(audio_path)
+        if init_image is None:
+            img = self.generate_batch(self.mel_features([audio]), [text_prompt], num_inference_steps, guidance_scale,
+                                      use_hierarchical=use_hierarchical, latents=self._request_latents(1, seed))
+            return self.to_pil(img)[0]
+        lat, eps = self._request_latents(1, seed, with_eps=True)
         img = self.generate_batch(self.mel_features([audio]), [text_prompt], num_inference_steps, guidance_scale,
-                                  use_hierarchical=use_hierarchical, latents=self._request_latents(1, seed))
+                                  use_hierarchical=use_hierarchical, latents=lat, init_images=init_image,
+                                  strength=strength, posterior_eps=eps if sample_posterior else None)
         return self.to_pil(img)[0]
 
     def batch_generate(self, audio_paths, text_prompts=None, **kwargs):
@@ -303,9 +379,18 @@ class AudioToImageInference:
         g = kwargs.get("guidance_scale", 7.5)
         seed = kwargs.get("seed", None)
         mel = self.mel_features([self.load_audio(p) for p in audio_paths])
+        init_images = kwargs.get("init_images", None)
+        if init_images is None:
+            img = self.generate_batch(mel, list(text_prompts), steps, g,
+                                      use_hierarchical=kwargs.get("use_hierarchical", True),
+                                      latents=self._request_latents(len(audio_paths), seed))
+            return self.to_pil(img)
+        # init_images= (one per item, or one for all), strength=, sample_posterior= as generate()
+        lat, eps = self._request_latents(len(audio_paths), seed, with_eps=True)
         img = self.generate_batch(mel, list(text_prompts), steps, g,
-                                  use_hierarchical=kwargs.get("use_hierarchical", True),
-                                  latents=self._request_latents(len(audio_paths), seed))
+                                  use_hierarchical=kwargs.get("use_hierarchical", True), latents=lat,
+                                  init_images=init_images, strength=kwargs.get("strength", 0.8),
+                                  posterior_eps=eps if kwargs.get("sample_posterior", True) else None)
         return self.to_pil(img)
 
     # ------------------------------------------------------------ batched core
@@ -348,40 +433,72 @@ class AudioToImageInference:
     @torch.no_grad()
     def generate_batch(self, mel: torch.Tensor, prompts: list[str] | None, num_inference_steps: int = 50,
                        guidance_scale: float = 7.5, seeds: list[int] | None = None, use_hierarchical: bool = True,
-                       ids: tuple | None = None, latents: torch.Tensor | None = None) -> torch.Tensor:
+                       ids: tuple | None = None, latents: torch.Tensor | None = None, init_images=None,
+                       strength: float = 0.8, posterior_eps: torch.Tensor | None = None,
+                       sample_posterior: bool = True) -> torch.Tensor:
         """mel [B, 1001, 64] on device -> uint8 images NHWC [B, H, W, 3] on device.  The
-        image size follows the latents ([B, 4, H/8, W/8]; default: the pipeline's size)."""
+        image size follows the latents ([B, 4, H/8, W/8]; default: the pipeline's size).
+        init_images (prepare_images forms; the pipeline's size): image-to-image.  The images are encoded, the
+        posterior sampled with posterior_eps [B, 4, H/8, W/8] (None: drawn after each sample's initial noise from
+        its seed's generator when sample_posterior, else the mode), noised with `latents` to
+        timesteps[t_start] (c2d_vae_posterior_noise, alpha read through the device step counter) and the last
+        steps - t_start steps run, t_start = DDIMScheduler.img2img_start(steps, strength)."""
         b = mel.shape[0]
         if ids is None:
             ids = (self.tokenizer([""] * b, self.device), self.tokenizer(prompts or [""] * b, self.device))
         ehs, kw, _ = self.condition(mel, ids[0], ids[1], use_hierarchical)
+        t_start = 0
+        if init_images is not None:
+            t_start = DDIMScheduler.img2img_start(num_inference_steps, strength)
+            imgs = self.prepare_images(init_images, b)
+            if latents is None and posterior_eps is None and sample_posterior:
+                latents, posterior_eps = initial_latents_and_eps(seeds if seeds is not None else list(range(b)),
+                                                                 self.height // 8, self.width // 8, self.device)
         if latents is None:
             latents = self.initial_latents(seeds if seeds is not None else list(range(b)))
         den = self.denoiser(b, num_inference_steps, guidance_scale, ehs, kw, latent_hw=tuple(latents.shape[-2:]))
         den.ehs.copy_(ehs)
         for k, v in kw["audio"].items():
             den.kw["audio"][k].copy_(v)
-        x = den.run(latents * self.scheduler.init_noise_sigma)
-        return self.vae(x)
+        if init_images is None:
+            x = den.run(latents * self.scheduler.init_noise_sigma)
+            return self.vae(x)
+        if tuple(latents.shape[-2:]) != (imgs.shape[1] // 8, imgs.shape[2] // 8):
+            raise ValueError(f"latents {tuple(latents.shape)} do not match init images {tuple(imgs.shape)}")
+        noise = latents.to(self.device, torch.float32).contiguous()
+        eps = posterior_eps.to(self.device, torch.float32).contiguous() if posterior_eps is not None else None
+        den.step_idx.fill_(t_start)   # the kernel reads the alpha of the first step that runs through the counter
+        x0 = ops.vae_posterior_noise(self.vae_encoder(imgs), torch.empty_like(noise), SCALING, eps=eps, noise=noise,
+                                     coef=den.coef, step_index=den.step_idx)
+        return self.vae(den.run(x0, start=t_start))
 
     @torch.no_grad()
     def generate_batch_graphed(self, wave: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor,
                                ids: tuple, latents: torch.Tensor, num_inference_steps: int = 50,
                                guidance_scale: float = 7.5, use_hierarchical: bool = True,
-                               slot: int = 0) -> torch.Tensor:
+                               slot: int = 0, init_images: torch.Tensor | None = None, strength: float = 0.8,
+                               posterior_eps: torch.Tensor | None = None) -> torch.Tensor:
         """generate_batch from device-resident inputs (48 kHz clips concatenated + offsets /
         lengths, token ids, latents) as hipGraphs: one graph for the conditioning leg, the
         denoise-step graph replayed per DDIM step, one graph for the VAE decode (BatchGraph).
         The graphs are built on the first call for a given batch / steps / guidance / size and
-        replayed afterwards with the new inputs copied into their static buffers."""
+        replayed afterwards with the new inputs copied into their static buffers.
+        init_images (uint8 [B, H, W, 3] on the device, the latents' size x 8): image-to-image.  The conditioning
+        graph then also runs the VAE encoder over a static image buffer, writes the noised latents into the
+        sampler state (c2d_vae_posterior_noise; posterior_eps None = the mode) and sets the step counter to
+        t_start; steps - t_start replays of the same step graph follow."""
+        t_start = 0
+        if init_images is not None:
+            t_start = DDIMScheduler.img2img_start(num_inference_steps, strength)
+            init_images = self.prepare_images(init_images, offsets.numel())
         key = (offsets.numel(), wave.numel(), num_inference_steps, float(guidance_scale), tuple(latents.shape),
-               bool(use_hierarchical), slot)
+               bool(use_hierarchical), slot, t_start, init_images is not None, posterior_eps is not None)
         bg = self._batch_graphs.get(key)
         if bg is None:
             bg = BatchGraph(self, wave, offsets, lengths, ids, latents, num_inference_steps, guidance_scale,
-                            use_hierarchical, slot)
+                            use_hierarchical, slot, init_images, t_start, posterior_eps)
             self._batch_graphs[key] = bg
-        return bg.run(wave, offsets, lengths, ids, latents)
+        return bg.run(wave, offsets, lengths, ids, latents, init_images, posterior_eps)
 
     @staticmethod
     def to_pil(images: torch.Tensor):
@@ -397,11 +514,19 @@ class BatchGraph:
       the GraphDenoiser step graph, replayed once per DDIM step (device step counter);
       g_vae  -- VAE decode of the final latents into a static uint8 image buffer.
     Inputs are copied into static device buffers, so a replay sees new audio, prompts and
-    latents; all workspaces come from the graphs' private pools (allocated at capture)."""
+    latents; all workspaces come from the graphs' private pools (allocated at capture).
+    With init images (img2img) g_cond also holds the VAE encoder over a static image buffer and
+    c2d_vae_posterior_noise writing the sampler state, and sets the step counter to t_start; the step graph
+    is the text-to-image one, replayed steps - t_start times."""
 
     def __init__(self, pipe: AudioToImageInference, wave, offsets, lengths, ids, latents, steps: int,
-                 guidance: float, use_hierarchical: bool, slot: int = 0):
+                 guidance: float, use_hierarchical: bool, slot: int = 0, init_images=None, t_start: int = 0,
+                 posterior_eps=None):
         self.pipe, self.steps, self.use_hier = pipe, steps, use_hierarchical
+        self.t_start = t_start
+        self.images = init_images.clone() if init_images is not None else None
+        self.eps = posterior_eps.float().clone() if posterior_eps is not None else None
+        self.enc = pipe.vae_encoder if init_images is not None else None
         self.wave, self.offs, self.lens = wave.clone(), offsets.clone(), lengths.clone()
         self.ids_u, self.ids_c = ids[0].clone(), ids[1].clone()
         self.lat = latents.float().clone()
@@ -437,16 +562,26 @@ class BatchGraph:
         for k, v in kw["audio"].items():
             den.kw["audio"][k].copy_(v)
         den.prepare_context()
-        den.x.copy_(self.lat * pipe.scheduler.init_noise_sigma)
-        den.step_idx.zero_()
+        if self.images is None:
+            den.x.copy_(self.lat * pipe.scheduler.init_noise_sigma)
+            den.step_idx.zero_()
+            return
+        den.step_idx.fill_(self.t_start)
+        ops.vae_posterior_noise(self.enc(self.images), den.x, SCALING, eps=self.eps, noise=self.lat, coef=den.coef,
+                                step_index=den.step_idx)
 
-    def run(self, wave, offsets, lengths, ids, latents) -> torch.Tensor:
-        for dst, src in ((self.wave, wave), (self.offs, offsets), (self.lens, lengths), (self.ids_u, ids[0]),
-                         (self.ids_c, ids[1]), (self.lat, latents)):
+    def run(self, wave, offsets, lengths, ids, latents, init_images=None, posterior_eps=None) -> torch.Tensor:
+        pairs = [(self.wave, wave), (self.offs, offsets), (self.lens, lengths), (self.ids_u, ids[0]),
+                 (self.ids_c, ids[1]), (self.lat, latents)]
+        if self.images is not None:
+            pairs.append((self.images, init_images))
+        if self.eps is not None:
+            pairs.append((self.eps, posterior_eps))
+        for dst, src in pairs:
             if src.data_ptr() != dst.data_ptr():
                 dst.copy_(src)
         self.g_cond.replay()
-        for _ in range(self.steps):
+        for _ in range(self.steps - self.t_start):
             self.den.graph.replay() if self.den.use_graph else self.den._body()
         self.g_vae.replay()
         self.pipe.last_denoiser = self.den
@@ -465,10 +600,13 @@ def main():
     ap.add_argument("--no_hierarchical", action="store_true", help="Disable hierarchical processing")
     ap.add_argument("--sd_model", type=str, default=None, help="diffusers-format SD1.5 folder (unet/, vae/, text_encoder/)")
     ap.add_argument("--clap_model", type=str, default=None, help="ClapModel weights file or folder")
+    ap.add_argument("--init_image", type=str, default=None, help="Start from this image (audio-guided img2img)")
+    ap.add_argument("--strength", type=float, default=0.8, help="img2img strength in (0, 1]: 1 = ignore the image")
     a = ap.parse_args()
     pipe = AudioToImageInference(checkpoint_dir=a.checkpoint_dir, sd_model_path=a.sd_model, clap_model_path=a.clap_model)
     img = pipe.generate(audio_path=a.audio, text_prompt=a.text, num_inference_steps=a.steps,
-                        guidance_scale=a.cfg_scale, seed=a.seed, use_hierarchical=not a.no_hierarchical)
+                        guidance_scale=a.cfg_scale, seed=a.seed, use_hierarchical=not a.no_hierarchical,
+                        init_image=a.init_image, strength=a.strength)
     img.save(a.output)
     print(f"Image saved to {a.output}")
 

@@ -90,14 +90,18 @@ class GraphDenoiser:
         self.step_idx.zero_()
 
     @torch.no_grad()
-    def run(self, latents: torch.Tensor) -> torch.Tensor:
-        """latents [B,4,h,w] (scaled by init_noise_sigma = 1) -> denoised latents fp32."""
+    def run(self, latents: torch.Tensor, start: int = 0) -> torch.Tensor:
+        """latents [B,4,h,w] (scaled by init_noise_sigma = 1) -> denoised latents fp32.
+        start: first step index (img2img: latents already noised to timesteps[start]); the device counter is
+        set to it and the same captured step is replayed steps - start times."""
+        if not 0 <= start < self.steps:
+            raise ValueError(f"start {start} outside [0, {self.steps})")
         self.prepare_context()
         if self.use_graph and self.graph is None:
             self.capture()
         self.x.copy_(latents)
-        self.step_idx.zero_()
-        for _ in range(self.steps):
+        self.step_idx.fill_(start)
+        for _ in range(self.steps - start):
             if self.use_graph:
                 self.graph.replay()
             else:

@@ -47,6 +47,23 @@ class DDIMScheduler:
         prev = a_p ** 0.5 * x0 + (1 - a_p) ** 0.5 * model_output
         return type("DDIMOutput", (), {"prev_sample": prev, "pred_original_sample": x0})()
 
+    @staticmethod
+    def img2img_start(num_inference_steps: int, strength: float) -> int:
+        """First step index of an image-to-image run (diffusers StableDiffusionImg2ImgPipeline.get_timesteps):
+        init = min(int(steps * strength), steps), t_start = max(steps - init, 0); the run starts from the
+        image noised to timesteps[t_start] and takes the last `init` steps."""
+        if not 0.0 <= strength <= 1.0:
+            raise ValueError(f"strength must be in [0, 1], got {strength}")
+        init = min(int(num_inference_steps * strength), num_inference_steps)
+        if init < 1:
+            raise ValueError(f"strength {strength} with {num_inference_steps} steps leaves no denoising step")
+        return max(num_inference_steps - init, 0)
+
+    def add_noise(self, original: torch.Tensor, noise: torch.Tensor, timestep: int) -> torch.Tensor:
+        """diffusers DDIMScheduler.add_noise at one timestep (host-side form of c2d_vae_posterior_noise)."""
+        a = self.alphas_cumprod[int(timestep)]
+        return a ** 0.5 * original + (1 - a) ** 0.5 * noise
+
     def device_tables(self, device) -> tuple[torch.Tensor, torch.Tensor]:
         """-> (t_table fp32 [S], coef fp32 [S, 2] = (alpha_t, alpha_prev))."""
         assert self.timesteps is not None, "call set_timesteps first"

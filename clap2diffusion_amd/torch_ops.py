@@ -18,14 +18,14 @@ import torch
 from torch import Tensor
 from torch.library import custom_op
 
-from ._lib import C2D_PRO_GN, C2D_PRO_LN, C2D_PRO_LNFOLD, C2D_PRO_NONE, C2D_PRO_SILU, ConvDesc, check, lib, ptr, stream_ptr
+from ._lib import C2D_PAD_AFTER, C2D_PAD_SAME, C2D_PRO_GN, C2D_PRO_LN, C2D_PRO_LNFOLD, C2D_PRO_NONE, C2D_PRO_SILU, ConvDesc, check, lib, ptr, stream_ptr
 
 _CU = "cuda"
 
 
 def _conv_desc(x, weight, kpad, cout, ksize, stride, up, x2, gn_scale, gn_shift, gn_silu, ln_stats, ln_gamma,
                ln_beta, silu_in, bias, act, temb, resid, out, src_pad=False, lnf_eps=0.0, gn_mom=None,
-               gn_groups=0, up_fold=False) -> ConvDesc:
+               gn_groups=0, up_fold=False, pad_after=False) -> ConvDesc:
     if x.dim() == 2:
         n, h, w = 1, 1, x.shape[0]
         c0 = x.shape[1]
@@ -37,6 +37,8 @@ def _conv_desc(x, weight, kpad, cout, ksize, stride, up, x2, gn_scale, gn_shift,
     if ksize == 3:
         vh, vw = (2 * h, 2 * w) if up or up_fold else (h, w)
         oh, ow = (vh + 2 - 3) // stride + 1, (vw + 2 - 3) // stride + 1
+        if pad_after:   # F.pad(x, (0, 1, 0, 1)) + conv(stride 2, padding 0): (h + 1 - 3) // 2 + 1
+            oh, ow = (h - 2) // 2 + 1, (w - 2) // 2 + 1
     else:
         oh, ow = h, w
     d = ConvDesc()
@@ -65,6 +67,7 @@ def _conv_desc(x, weight, kpad, cout, ksize, stride, up, x2, gn_scale, gn_shift,
     d.src_pad = int(src_pad)
     if gn_mom is not None:
         d.gn_mom = ptr(gn_mom); d.gn_groups = gn_groups
+    d.pad_mode = C2D_PAD_AFTER if pad_after else C2D_PAD_SAME
     return d
 
 
@@ -77,16 +80,19 @@ def conv2d_igemm(x: Tensor, weight: Tensor, kpad: int, cout: int, ksize: int, st
                  ln_stats: Optional[Tensor], ln_gamma: Optional[Tensor], ln_beta: Optional[Tensor], silu_in: bool,
                  bias: Optional[Tensor], act: int, temb: Optional[Tensor], resid: Optional[Tensor],
                  out: Tensor, src_pad: bool = False, lnf_eps: float = 0.0, gn_mom: Optional[Tensor] = None,
-                 gn_groups: int = 0, up_fold: bool = False) -> None:
+                 gn_groups: int = 0, up_fold: bool = False, pad_after: bool = False) -> None:
     """c2d_conv2d_igemm (+ its split-K workspace, sized by c2d_conv2d_igemm_workspace_size).
     src_pad: x is the zero-bordered layout [n][h + 2][w + 2][c] (c2d_groupnorm_pad).
     lnf_eps > 0: a LayerNorm (that eps) folded into the GEMM (C2D_PRO_LNFOLD).
     gn_mom: fp32 [n][hw / rows][gn_groups][2], the output's GroupNorm moments written by the conv
     (c2d_conv_desc::gn_mom; rows = c2d_conv2d_gn_rows).
     up_fold: the folded upsample (c2d_conv_desc::up = 2): x low-res, weight the [4][cout][4 cin] phase pack, out
-    [n][2h][2w][cout]; `up` stays the nearest-x2 view of the register-staged 3x3."""
+    [n][2h][2w][cout]; `up` stays the nearest-x2 view of the register-staged 3x3.
+    pad_after: c2d_conv_desc::pad_mode = C2D_PAD_AFTER, the 3x3 stride-2 conv of F.pad(x, (0, 1, 0, 1)) with
+    padding 0 (even h, w; out [n][h / 2][w / 2][cout])."""
     d = _conv_desc(x, weight, kpad, cout, ksize, stride, up, x2, gn_scale, gn_shift, gn_silu, ln_stats, ln_gamma,
-                   ln_beta, silu_in, bias, act, temb, resid, out, src_pad, lnf_eps, gn_mom, gn_groups, up_fold)
+                   ln_beta, silu_in, bias, act, temb, resid, out, src_pad, lnf_eps, gn_mom, gn_groups, up_fold,
+                   pad_after)
     wsb = lib().c2d_conv2d_igemm_workspace_size(ctypes.byref(d))
     if wsb:
         ws = torch.empty(wsb // 4, device=x.device, dtype=torch.float32)
@@ -100,7 +106,8 @@ def conv2d_igemm(x: Tensor, weight: Tensor, kpad: int, cout: int, ksize: int, st
 
 @conv2d_igemm.register_fake
 def _(x, weight, kpad, cout, ksize, stride, up, x2, gn_scale, gn_shift, gn_silu, ln_stats, ln_gamma, ln_beta,
-      silu_in, bias, act, temb, resid, out, src_pad=False, lnf_eps=0.0, gn_mom=None, gn_groups=0, up_fold=False):
+      silu_in, bias, act, temb, resid, out, src_pad=False, lnf_eps=0.0, gn_mom=None, gn_groups=0, up_fold=False,
+      pad_after=False):
     return None
 
 
@@ -266,6 +273,25 @@ def latent_to_nhwc(x: Tensor, cpad: int, dup: bool, out: Tensor) -> None:
           "c2d_latent_to_nhwc")
 
 
+@custom_op("c2d::image_to_nhwc", mutates_args=("out",), device_types=_CU)
+def image_to_nhwc(img: Tensor, out: Tensor) -> None:
+    """c2d_image_to_nhwc: uint8 [n][h][w][3] -> fp16 [n][h][w][8], u / 127.5 - 1 and five zero channels."""
+    n, h, w, _ = img.shape
+    check(lib().c2d_image_to_nhwc(ptr(img), n, h * w, ptr(out), stream_ptr()), "c2d_image_to_nhwc")
+
+
+@custom_op("c2d::vae_posterior_noise", mutates_args=("x",), device_types=_CU)
+def vae_posterior_noise(moments: Tensor, eps: Optional[Tensor], noise: Optional[Tensor], coef: Optional[Tensor],
+                        step_index: Optional[Tensor], scaling: float, x: Tensor) -> None:
+    """c2d_vae_posterior_noise: moments fp16 [n * hw][ld] -> x fp32 [n][4][h][w] (sample or mode, * scaling,
+    add_noise at coef[*step_index] when noise is given)."""
+    n = x.shape[0]
+    hw = x.numel() // (4 * n)
+    check(lib().c2d_vae_posterior_noise(ptr(moments), moments.stride(0), ptr(eps), ptr(noise), ptr(coef),
+                                        ptr(step_index), n, hw, scaling, ptr(x), stream_ptr()),
+          "c2d_vae_posterior_noise")
+
+
 @custom_op("c2d::upsample_nearest2x", mutates_args=("out",), device_types=_CU)
 def upsample_nearest2x(x: Tensor, out: Tensor) -> None:
     n, h, w, c = x.shape
@@ -280,11 +306,12 @@ def add(a: Tensor, b: Tensor, out: Tensor) -> None:
 # fake (meta) implementations: every op only mutates caller-allocated outputs
 for _op in (pack_weights, groupnorm_stats, groupnorm_apply, groupnorm, groupnorm_pad, groupnorm_moments, layernorm_stats, layernorm, attention_fwd,
             attention_small, window_attention, htsat_mel_patches, patch_merge_gather, row_mean, softmax_rows,
-            l2_normalize, clap_log_mel, timestep_embedding, cfg_ddim_step, latent_to_nhwc, upsample_nearest2x, add):
+            l2_normalize, clap_log_mel, timestep_embedding, cfg_ddim_step, latent_to_nhwc, upsample_nearest2x, add,
+            image_to_nhwc, vae_posterior_noise):
     _op.register_fake(lambda *args, **kwargs: None)
 
 OPS = ("conv2d_igemm", "pack_weights", "groupnorm_stats", "groupnorm_apply", "groupnorm", "groupnorm_pad", "groupnorm_moments",
        "layernorm_stats",
        "layernorm", "attention_fwd", "attention_small", "window_attention", "htsat_mel_patches", "patch_merge_gather",
        "row_mean", "softmax_rows", "l2_normalize", "clap_log_mel", "timestep_embedding", "cfg_ddim_step",
-       "latent_to_nhwc", "upsample_nearest2x", "add")
+       "latent_to_nhwc", "upsample_nearest2x", "add", "image_to_nhwc", "vae_posterior_noise")

@@ -1,4 +1,5 @@
-"""SD1.5 AutoencoderKL decoder (latent [B,4,h,w] -> image [B,8h,8w,3] uint8).
+"""SD1.5 AutoencoderKL decoder (latent [B,4,h,w] -> image [B,8h,8w,3] uint8) and encoder (image ->
+posterior moments -> latent, the img2img leg).
 
 SURVEY.md §8(f) "next" #1.  Convolutions, GroupNorm(+SiLU) and the resnet /
 upsample structure reuse the UNet's HIP kernels (NHWC fp16, implicit GEMM with
@@ -6,6 +7,9 @@ fused GN prologue and residual epilogue); the single-head d=512 mid-block
 attention is materialised per image on the same GEMM kernel (S = Q K^T, HIP row
 softmax, O = P V) -- a 512-wide head does not fit the flash kernel's registers.
 diffusers-0.23.1 AutoencoderKL decoder keys (post_quant_conv.*, decoder.*).
+The encoder (encoder.*, quant_conv.*) is the same kernels run the other way: its three downsamplers are
+the pad-after stride-2 3x3 (c2d_conv_desc::pad_mode), its input comes through c2d_image_to_nhwc and its
+moments leave through c2d_vae_posterior_noise.
 """
 from __future__ import annotations
 
@@ -123,3 +127,89 @@ class VAEDecoder(nn.Module):
         x = d.conv_out(d.conv_norm_out.apply(x, silu=True))
         img = (x[..., :3].float() / 2 + 0.5).clamp_(0, 1)
         return (img * 255).round_().to(torch.uint8)
+
+
+class EncoderDownsample2D(nn.Module):
+    """diffusers Downsample2D(padding=0): F.pad(x, (0, 1, 0, 1)) + conv(3x3, stride 2, padding 0), as one
+    pad-after conv (no padded tensor)."""
+
+    def __init__(self, c: int):
+        super().__init__()
+        self.conv = HConv2d(c, c, 3, stride=2, pad_after=True)
+
+    def forward(self, x):
+        return self.conv(x)
+
+
+class VAEEncoder(nn.Module):
+    """uint8 image [B,H,W,3] -> posterior moments (mean | log-variance) -> latents [B,4,H/8,W/8]."""
+
+    def __init__(self, cfg: dict = SD15_VAE):
+        super().__init__()
+        ch = list(cfg["block_out_channels"])
+        g = cfg["norm_groups"]
+        self.lc = cfg["latent_channels"]
+        enc = nn.Module()
+        enc.conv_in = HConv2d(cfg["out_channels"], ch[0], 3, cin_pad=8)   # RGB + 5 zero channels (c2d_image_to_nhwc)
+        enc.down_blocks = nn.ModuleList()
+        out_c = ch[0]
+        for i, c in enumerate(ch):
+            blk = nn.Module()
+            prev, out_c = out_c, c
+            blk.resnets = nn.ModuleList([ResnetBlock2D(prev if j == 0 else out_c, out_c, 0, g, 1e-6)
+                                         for j in range(cfg["layers_per_block"])])
+            if i < len(ch) - 1:
+                blk.downsamplers = nn.ModuleList([EncoderDownsample2D(out_c)])
+            enc.down_blocks.append(blk)
+        enc.mid_block = nn.Module()
+        enc.mid_block.resnets = nn.ModuleList([ResnetBlock2D(ch[-1], ch[-1], 0, g, 1e-6),
+                                               ResnetBlock2D(ch[-1], ch[-1], 0, g, 1e-6)])
+        enc.mid_block.attentions = nn.ModuleList([VAEAttention(ch[-1], g)])
+        enc.conv_norm_out = HGroupNorm(g, ch[-1], 1e-6)
+        enc.conv_out = HConv2d(ch[-1], 2 * self.lc, 3)
+        self.encoder = enc
+        self.quant_conv = HConv2d(2 * self.lc, 2 * self.lc, 1)
+
+    @torch.no_grad()
+    def load_diffusers_state_dict(self, sd: dict) -> None:
+        used = set()
+        for name, m in self.named_modules():
+            if isinstance(m, (HLinear, HConv2d, HGroupNorm)):
+                m.load(sd[name + ".weight"], sd.get(name + ".bias"))
+                used |= {name + ".weight", name + ".bias"}
+        left = [k for k in sd if k not in used]
+        if left:
+            raise KeyError(f"unused VAE encoder keys: {left[:4]}")
+        self.encoder.mid_block.attentions[0].finalize()
+
+    @staticmethod
+    def check_size(h: int, w: int) -> None:
+        if h <= 0 or w <= 0 or h % 64 or w % 64:
+            raise ValueError(f"VAE encoder images must be multiples of 64 pixels on both sides, got {h} x {w} "
+                             "(three stride-2 stages, and the mid-block attention needs (H/8)(W/8) % 64 == 0)")
+
+    @torch.no_grad()
+    def forward(self, images: torch.Tensor) -> torch.Tensor:
+        """uint8 NHWC [B,H,W,3] on the device -> moments fp16 [B * H/8 * W/8, 8] (mean | log-variance)."""
+        if images.dim() != 4 or images.shape[-1] != 3 or images.dtype != torch.uint8:
+            raise ValueError(f"images must be uint8 [B, H, W, 3], got {images.dtype} {tuple(images.shape)}")
+        self.check_size(images.shape[1], images.shape[2])
+        e = self.encoder
+        x = e.conv_in(ops.image_to_nhwc(images.contiguous()))
+        for blk in e.down_blocks:
+            for r in blk.resnets:
+                x = r(x)
+            if hasattr(blk, "downsamplers"):
+                x = blk.downsamplers[0](x)
+        x = e.mid_block.resnets[0](x)
+        x = e.mid_block.attentions[0](x)
+        x = e.mid_block.resnets[1](x)
+        x = e.conv_out(e.conv_norm_out.apply(x, silu=True))
+        return self.quant_conv(x).view(-1, 2 * self.lc)
+
+    @torch.no_grad()
+    def encode(self, images: torch.Tensor, eps: torch.Tensor | None = None) -> torch.Tensor:
+        """-> scaled latents fp32 [B,4,H/8,W/8]: (mean + std * eps) * 0.18215, eps None = the posterior mode."""
+        b, h, w, _ = images.shape
+        out = torch.empty(b, self.lc, h // 8, w // 8, device=images.device, dtype=torch.float32)
+        return ops.vae_posterior_noise(self.forward(images), out, SCALING, eps=eps)

@@ -150,6 +150,51 @@ def vae_decoder_param_shapes(cfg: dict = SD15_VAE) -> "OrderedDict[str, tuple]":
     return S
 
 
+def vae_encoder_param_shapes(cfg: dict = SD15_VAE) -> "OrderedDict[str, tuple]":
+    """diffusers AutoencoderKL encoder + quant_conv keys (SD1.5 topology): conv_in 3 -> 128, four
+    DownEncoderBlock2D of two resnets (128, 256, 512, 512) with a downsampler after the first three, the mid
+    block (resnet, one-head attention, resnet), conv_norm_out, conv_out 512 -> 2 x latent, quant_conv 1x1."""
+    S: "OrderedDict[str, tuple]" = OrderedDict()
+    ch = list(cfg["block_out_channels"])
+
+    def conv(p, i, o, k):
+        S[p + ".weight"] = (o, i, k, k)
+        S[p + ".bias"] = (o,)
+
+    def norm(p, c):
+        S[p + ".weight"] = (c,)
+        S[p + ".bias"] = (c,)
+
+    def resnet(p, i, o):
+        norm(p + ".norm1", i)
+        conv(p + ".conv1", i, o, 3)
+        norm(p + ".norm2", o)
+        conv(p + ".conv2", o, o, 3)
+        if i != o:
+            conv(p + ".conv_shortcut", i, o, 1)
+
+    lc = cfg["latent_channels"]
+    conv("encoder.conv_in", cfg["out_channels"], ch[0], 3)
+    out_c = ch[0]
+    for i, c in enumerate(ch):
+        prev, out_c = out_c, c
+        for j in range(cfg["layers_per_block"]):
+            resnet(f"encoder.down_blocks.{i}.resnets.{j}", prev if j == 0 else out_c, out_c)
+        if i < len(ch) - 1:
+            conv(f"encoder.down_blocks.{i}.downsamplers.0.conv", out_c, out_c, 3)
+    resnet("encoder.mid_block.resnets.0", ch[-1], ch[-1])
+    a = "encoder.mid_block.attentions.0"
+    norm(a + ".group_norm", ch[-1])
+    for n in ("to_q", "to_k", "to_v", "to_out.0"):
+        S[f"{a}.{n}.weight"] = (ch[-1], ch[-1])
+        S[f"{a}.{n}.bias"] = (ch[-1],)
+    resnet("encoder.mid_block.resnets.1", ch[-1], ch[-1])
+    norm("encoder.conv_norm_out", ch[-1])
+    conv("encoder.conv_out", ch[-1], 2 * lc, 3)
+    conv("quant_conv", 2 * lc, 2 * lc, 1)
+    return S
+
+
 def key_seed(base: int, key: str) -> int:
     return (base * 1000003 + zlib.crc32(key.encode())) % (2 ** 31 - 1)
 
@@ -190,6 +235,10 @@ def synth_unet(seed: int = 0, device="cpu", dtype=torch.float32, cfg: dict = SD1
 
 def synth_vae_decoder(seed: int = 0, device="cpu", dtype=torch.float32, cfg: dict = SD15_VAE):
     return synth_state_dict(vae_decoder_param_shapes(cfg), seed + 17, device, dtype)
+
+
+def synth_vae_encoder(seed: int = 0, device="cpu", dtype=torch.float32, cfg: dict = SD15_VAE):
+    return synth_state_dict(vae_encoder_param_shapes(cfg), seed + 29, device, dtype)
 
 
 def synth_processor_weights(level: str, seed: int = 0, audio_dim: int = 768, hidden_dim: int = 768,
@@ -433,6 +482,34 @@ def vae_decoder_state_dict(sd: dict) -> "OrderedDict[str, torch.Tensor]":
     if "post_quant_conv.weight" not in out:
         raise KeyError("no AutoencoderKL decoder keys (decoder.* / post_quant_conv.*) in checkpoint")
     return out
+
+
+vae_state_dict = vae_decoder_state_dict   # the half the text-to-image path loads
+
+
+def vae_encoder_state_dict(sd: dict) -> "OrderedDict[str, torch.Tensor]":
+    """Encoder half of an AutoencoderKL state dict (encoder.*, quant_conv.*), with the old mid-block
+    attention names renamed and their 1x1-conv weights flattened to Linear, as vae_decoder_state_dict."""
+    out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    for k, v in sd.items():
+        if not (k.startswith("encoder.") or k.startswith("quant_conv.")):
+            continue
+        parts = k.split(".")
+        if "attentions" in parts and len(parts) >= 2 and parts[-2] in _VAE_OLD_ATTN:
+            k = ".".join(parts[:-2] + [_VAE_OLD_ATTN[parts[-2]], parts[-1]])
+            if v.dim() == 4:
+                v = v[:, :, 0, 0]
+        out[k] = v
+    if "quant_conv.weight" not in out:
+        raise KeyError("no AutoencoderKL encoder keys (encoder.* / quant_conv.*) in checkpoint")
+    return out
+
+
+def load_sd15_vae_encoder(folder) -> "OrderedDict[str, torch.Tensor]":
+    """The AutoencoderKL encoder keys from a diffusers-format SD1.5 folder (its vae/ file), for img2img;
+    load_sd15_folder keeps returning the decoder half only."""
+    from pathlib import Path
+    return vae_encoder_state_dict(load_weights_file(find_weights_file(Path(folder) / "vae")))
 
 
 def load_sd15_folder(folder) -> dict:

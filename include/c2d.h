@@ -55,6 +55,10 @@ extern "C" {
 #define C2D_ACT_SILU 4
 #define C2D_ACT_QUICK_GELU 5 /* x * sigmoid(1.702 x) (CLIP text MLP, transformers ACT2FN["quick_gelu"]) */
 
+/* c2d_conv_desc::pad_mode: where a 3x3 conv's zero padding goes */
+#define C2D_PAD_SAME 0       /* one pixel on every side (padding = 1)                                      */
+#define C2D_PAD_AFTER 1      /* one pixel after the last row / column only, stride 2 (see c2d_conv_desc)   */
+
 /*
  * Implicit-GEMM convolution / linear layer on MFMA (v_mfma_f32_16x16x32_f16).
  *   out[m, j] = act( sum_k A[m,k] * W[j,k] + bias[j] ) + temb[n(m), j] + resid[m, j]
@@ -87,6 +91,20 @@ extern "C" {
  * the 16x16x32 LDS-DMA tiles (1, 2, 3, 7, 8, 9, 80, 81), split-K included; never on the row-ring tiles,
  * the panel GEMM, tile 50 or the 32x32 tiles -- a forced plan naming one of those is ignored.
  * A library built with -DC2D_TUNE_UPFOLD=0 (A/B only) answers C2D_E_SHAPE to up = 2.
+ *
+ * Pad-after downsample (pad_mode = C2D_PAD_AFTER): diffusers Downsample2D(padding = 0) as the AutoencoderKL
+ * encoder uses it, F.pad(x, (0, 1, 0, 1)) followed by a 3x3 stride-2 conv with padding 0, without the padded
+ * tensor.  Output (oy, ox) reads the window with origin (2 oy, 2 ox); input row h and input column w read as
+ * zero.  For even h the output size equals the pad-1 conv's, so oh / ow cannot tell the two apart: the mode does.
+ *   shape   ksize = 3, stride = 2, up = 0, src_pad = 0, h and w even, oh = h / 2, ow = w / 2; anything else
+ *           C2D_E_SHAPE.  A pad_mode outside {0, 1}: C2D_E_ARG.
+ *   taken   one or two sources, bias, resid, temb, the prologues, gn_mom where c2d_conv2d_gn_rows allows.
+ * The plan, workspace and gn_rows queries answer for the mode as the launch behaves (the plan query with the
+ * same error codes, the other two with 0).  It plans exactly as the pad-1 stride-2 conv of the same shape and
+ * runs on every kernel that one can: the register-staged kernel, the 16x16x32 LDS-DMA tiles (1, 2, 3, 7, 8, 9,
+ * 80, 81), the 32x32 tiles (25, 28, 29) and the ping-pong tiles 40 / 41, split-K included -- all take the
+ * window origin from one runtime parameter.  Never the row-ring tiles (they need src_pad), the panel GEMM or
+ * tile 50 (1x1 only): a forced plan naming one of those is ignored.
  *
  * Replaces (diffusers 0.23.1): ResnetBlock2D.norm1/2+SiLU+conv1/conv2+temb add+
  * shortcut, Downsample2D/Upsample2D convs, conv_in/conv_out, Transformer2DModel
@@ -142,6 +160,10 @@ typedef struct c2d_conv_desc {
        this library: the descriptor grew (c2d_version "r6").                              */
     void* gn_mom;
     int gn_groups;           /* channel groups of the moments (cout % gn_groups == 0)     */
+    /* r7: C2D_PAD_SAME (0, the behaviour of every earlier version: a zero-initialised descriptor is
+       unchanged) or C2D_PAD_AFTER (the pad-after stride-2 3x3 above).  Appended: callers built against
+       the r6 header must zero the descriptor's tail or not be mixed with this library (c2d_version "r7") */
+    int pad_mode;
 } c2d_conv_desc;
 
 int c2d_conv2d_igemm(const c2d_conv_desc* d, void* stream);
@@ -428,6 +450,27 @@ int c2d_cfg_ddim_step(const void* eps, float* x, int b, int c, int hw, float gui
  * duplication for the CFG pair (dup=1 writes rows n..2n-1 again). */
 int c2d_latent_to_nhwc(const float* x, int n, int c, int hw, int cpad, int dup, void* out,
                        void* stream);
+
+/* uint8 NHWC image [n][hw][3] -> fp16 NHWC [n][hw][8]: channel c < 3 = (float)u / 127.5f - 1.0f rounded to
+ * fp16 (the [-1, 1] range AutoencoderKL.encode expects, diffusers VaeImageProcessor.normalize), channels 3..7
+ * zero, so the encoder's conv_in reads 16-B pixels (cin_pad = 8).  One 16-B store per pixel; out 16-B aligned. */
+int c2d_image_to_nhwc(const uint8_t* img, int n, int hw, void* out, void* stream);
+
+/*
+ * Posterior sample + latent scaling + layout change + scheduler add_noise in one launch (the img2img entry
+ * into the DDIM loop).  moments fp16 [n * hw][ld] (ld >= 8): channels 0..3 the mean, 4..7 the log-variance
+ * (the AutoencoderKL quant_conv output).  eps, noise fp32 NCHW [n][4][hw] or NULL; x fp32 NCHW [n][4][hw].
+ *   z = (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps) * scaling      eps NULL: the mode, mean * scaling
+ *   noise NULL: x = z (a plain encode; coef / step_index unused)
+ *   else a = coef[2 * (*step_index)], x = sqrt(a) z + sqrt(1 - a) noise
+ * coef is the (alpha_t, alpha_prev) table c2d_cfg_ddim_step reads, so a is the alpha of the first step that
+ * will run and the step is read on the device: graph-capturable, no host read of the counter.  fp32 arithmetic.
+ * Replaces diffusers DiagonalGaussianDistribution.sample / .mode, the * scaling_factor of the img2img
+ * pipeline's prepare_latents and DDIMScheduler.add_noise at timesteps[t_start] (diffusers 0.23.1).
+ */
+int c2d_vae_posterior_noise(const void* moments, int ld, const float* eps, const float* noise,
+                            const float* coef, const int* step_index, int n, int hw, float scaling, float* x,
+                            void* stream);
 
 /* Nearest-neighbour x2 upsample of NHWC fp16 [n, h, w, c] -> [n, 2h, 2w, c], c % 8 == 0.
  * Replaces F.interpolate(scale_factor=2.0, mode="nearest") in diffusers Upsample2D
