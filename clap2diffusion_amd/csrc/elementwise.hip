@@ -292,7 +292,7 @@ extern "C" int c2d_vae_posterior_noise(const void* moments, int ld, const float*
 
 extern "C" int c2d_latent_to_nhwc(const float* x, int n, int c, int hw, int cpad, int dup, void* out, void* stream) {
     if (!x || !out) return C2D_E_ARG;
-    if (cpad < c || n <= 0) return C2D_E_SHAPE;
+    if (cpad < c || n <= 0 || c <= 0 || hw <= 0) return C2D_E_SHAPE;
     const int tot = n * hw * cpad;
     hipLaunchKernelGGL(latent_to_nhwc_kernel, dim3((tot + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, n, c,
                        hw, cpad, dup, (f16*)out);
@@ -348,7 +348,7 @@ extern "C" int c2d_htsat_mel_patches(const float* mel, int b, int t, const float
 
 extern "C" int c2d_patch_merge_gather(const void* x, int b, int h, int w, int c, void* out, void* stream) {
     if (!x || !out) return C2D_E_ARG;
-    if ((h & 1) || (w & 1) || (c & 7)) return C2D_E_SHAPE;
+    if (b <= 0 || h <= 0 || w <= 0 || c <= 0 || (h & 1) || (w & 1) || (c & 7)) return C2D_E_SHAPE;
     if (!aligned16(x) || !aligned16(out)) return C2D_E_ALIGN;
     const size_t tot = (size_t)b * (h / 2) * (w / 2) * 4 * (c / 8);
     hipLaunchKernelGGL(patch_merge_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
@@ -358,6 +358,7 @@ extern "C" int c2d_patch_merge_gather(const void* x, int b, int h, int w, int c,
 
 extern "C" int c2d_row_mean(const void* x, int b, int rows, int c, int ld, float* out, void* stream) {
     if (!x || !out) return C2D_E_ARG;
+    if (b <= 0 || rows <= 0 || c <= 0 || ld < c) return C2D_E_SHAPE;
     const int tot = b * c;
     hipLaunchKernelGGL(row_mean_kernel, dim3((tot + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const f16*)x, b,
                        rows, c, ld, out);
@@ -366,6 +367,7 @@ extern "C" int c2d_row_mean(const void* x, int b, int rows, int c, int ld, float
 
 extern "C" int c2d_l2_normalize(float* x, int m, int c, void* stream) {
     if (!x) return C2D_E_ARG;
+    if (m <= 0 || c <= 0) return C2D_E_SHAPE;
     hipLaunchKernelGGL(l2norm_kernel, dim3(m), dim3(256), 0, (hipStream_t)stream, x, m, c);
     return check_launch();
 }

@@ -376,14 +376,20 @@ int c2d_htsat_mel_patches(const float* mel, int b, int t, const float* bn_scale,
                           const float* bn_shift, void* out, void* stream);
 
 /* Swin PatchMerging gather: [b][h][w][c] -> [b][h/2*w/2][4c] in the
- * (r0c0, r1c0, r0c1, r1c1) order of ClapAudioPatchMerging.forward (modeling_clap.py:700-717). */
+ * (r0c0, r1c0, r0c1, r1c1) order of ClapAudioPatchMerging.forward (modeling_clap.py:700-717).
+ * C2D_E_SHAPE, before any launch: b, h, w or c <= 0, h or w odd, c % 8 != 0.
+ * C2D_E_ALIGN: x or out not 16-byte aligned. */
 int c2d_patch_merge_gather(const void* x, int b, int h, int w, int c, void* out, void* stream);
 
 /* Row mean over groups of `rows` consecutive rows: out fp32 [b][c] = mean_r x[b*rows+r][c]
- * (ClapAudioEncoder avgpool over the final 64 tokens, modeling_clap.py:880-896). */
+ * (ClapAudioEncoder avgpool over the final 64 tokens, modeling_clap.py:880-896).
+ * x fp16 with leading dimension ld (elements).  C2D_E_SHAPE, before any launch: b, rows or
+ * c <= 0 (rows = 0 has no mean), ld < c. */
 int c2d_row_mean(const void* x, int b, int rows, int c, int ld, float* out, void* stream);
 
-/* Row-wise L2 normalise fp32 [m][c] in place (F.normalize, modeling_clap.py:1533). */
+/* Row-wise L2 normalise fp32 [m][c] in place (F.normalize, modeling_clap.py:1533): x / max(||x||, 1e-12),
+ * so an all-zero row stays zero.  The sum of squares is fp32: elements up to ~1e18 in magnitude.
+ * C2D_E_SHAPE, before any launch: m <= 0 or c <= 0. */
 int c2d_l2_normalize(float* x, int m, int c, void* stream);
 
 /* Short-sequence attention, l <= 128 keys = queries, d = 64, optional causal mask
@@ -447,7 +453,8 @@ int c2d_cfg_ddim_step(const void* eps, float* x, int b, int c, int hw, float gui
                       const float* coef, int* step_index, int advance, void* stream);
 
 /* NCHW fp32 [n][c][hw] -> NHWC fp16 [2*n or n][hw][cpad] (zero-padded channels), optional
- * duplication for the CFG pair (dup=1 writes rows n..2n-1 again). */
+ * duplication for the CFG pair (dup=1 writes rows n..2n-1 again).
+ * C2D_E_SHAPE, before any launch: n, c or hw <= 0, cpad < c. */
 int c2d_latent_to_nhwc(const float* x, int n, int c, int hw, int cpad, int dup, void* out,
                        void* stream);
 

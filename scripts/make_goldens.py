@@ -19,10 +19,16 @@ Run here (not on the GPU box, where /root/reference does not exist):
                   varies over queries.
   htsat.npz       transformers ClapModel.get_audio_features (the call at
                   models/audio_encoder.py:171-174) on synthetic HTSAT weights and seeded mel input.
+  htsat_ext.npz   the same call at other clip lengths: T = 1024 (no resize), 300 and 2 (the
+                  shortest clip the bicubic resize takes).  Only the recipe (T, batch, seed) and the
+                  outputs are stored; the tests regenerate the mel from the seed.
 Only inputs and outputs are stored; weights are regenerated from their seeds.
+
+    python scripts/make_goldens.py --only htsat_ext    writes tests/golden/htsat_ext.npz alone
 """
 from __future__ import annotations
 
+import argparse
 import sys
 import types
 from pathlib import Path
@@ -97,8 +103,45 @@ class MiniAttention(nn.Module):
         return s.softmax(dim=-1)
 
 
+HTSAT_EXT_CASES = ((1024, 1, 1024), (300, 2, 300), (2, 1, 2))   # (T, batch, seed)
+
+
+def clap_model():
+    """transformers ClapModel (the reference's CLAP dependency) holding synth_htsat(0)."""
+    from transformers import ClapConfig, ClapModel
+    model = ClapModel(ClapConfig()).eval()
+    sd = model.state_dict()
+    syn = synth_htsat(0)
+    missing = [k for k in sd if (k.startswith("audio_model") or k.startswith("audio_projection"))
+               and k not in syn and "relative_position_index" not in k and "num_batches_tracked" not in k]
+    assert not missing, missing
+    for k, v in syn.items():
+        assert tuple(sd[k].shape) == tuple(v.shape), k
+    model.load_state_dict({**sd, **syn})
+    return model
+
+
+def write_htsat_ext(model) -> None:
+    ext = {"recipe": np.array(HTSAT_EXT_CASES, dtype=np.int64)}
+    for t, b, seed in HTSAT_EXT_CASES:
+        mel = torch.randn(b, 1, t, 64, generator=torch.Generator().manual_seed(seed)) * 2.0 - 4.0
+        with torch.no_grad():
+            ext[f"t{t}_embedding"] = model.get_audio_features(input_features=mel).pooler_output.numpy()
+            ext[f"t{t}_pooled"] = model.audio_model(input_features=mel).pooler_output.numpy()
+    np.savez_compressed(OUT / "htsat_ext.npz", **ext)
+
+
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--only", choices=("all", "htsat_ext"), default="all",
+                    help="htsat_ext: write tests/golden/htsat_ext.npz and leave every other file alone")
+    args = ap.parse_args()
     torch.manual_seed(0)
+    OUT.mkdir(parents=True, exist_ok=True)
+    if args.only == "htsat_ext":
+        write_htsat_ext(clap_model())
+        print("htsat_ext.npz", (OUT / "htsat_ext.npz").stat().st_size)
+        return
     AudioAdapter, AudioAttnProcessor, HierarchicalAudioV4, Improved = load_reference()
     OUT.mkdir(parents=True, exist_ok=True)
 
@@ -186,22 +229,14 @@ def main():
     np.savez_compressed(OUT / "processor_ext.npz", **ext)
 
     # ---------------- HTSAT (transformers ClapModel, the reference's CLAP dependency)
-    from transformers import ClapConfig, ClapModel
-    model = ClapModel(ClapConfig()).eval()
-    sd = model.state_dict()
-    syn = synth_htsat(0)
-    missing = [k for k in sd if (k.startswith("audio_model") or k.startswith("audio_projection"))
-               and k not in syn and "relative_position_index" not in k and "num_batches_tracked" not in k]
-    assert not missing, missing
-    for k, v in syn.items():
-        assert tuple(sd[k].shape) == tuple(v.shape), k
-    model.load_state_dict({**sd, **syn})
+    model = clap_model()
     gm = torch.Generator().manual_seed(77)
     mel = torch.randn(2, 1, 1001, 64, generator=gm) * 2.0 - 4.0
     with torch.no_grad():
         emb = model.get_audio_features(input_features=mel).pooler_output
         pooled = model.audio_model(input_features=mel).pooler_output
     np.savez_compressed(OUT / "htsat.npz", mel=mel.numpy(), embedding=emb.numpy(), pooled=pooled.numpy())
+    write_htsat_ext(model)
     for f in sorted(OUT.glob("*.npz")):
         print(f.name, f.stat().st_size)
 

@@ -74,3 +74,76 @@ def test_new_entry_points_validate_before_launch():
     assert L.c2d_softmax_rows(aligned, 4, 16392, 16392, aligned, 16392, None) == -2
     assert L.c2d_softmax_rows(aligned, 4, 16, 20, aligned, 16, None) == -3
     assert L.c2d_softmax_rows(aligned, 0, 16, 16, aligned, 16, None) == 0
+
+
+def test_htsat_entry_points_validate_before_launch():
+    """The audio tower's kernels and the small elementwise ones: documented C2D_E_* codes on arguments
+    that cannot be right, nothing launched (bogus non-null pointers, never dereferenced)."""
+    import torch  # noqa: F401
+    from clap2diffusion_amd import _lib
+    L = _lib.lib()
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)      # 16-byte aligned
+    odd = ctypes.c_void_p(p.value + 2)
+    OK, ARG, SHAPE, ALIGN = 0, -1, -2, -3
+    # c2d_window_attention(qkv, ld_qkv, row_map, n_windows, heads, d, bias, mask, n_mask, out, ldo, stream)
+    wa = L.c2d_window_attention
+    assert wa(None, 288, p, 4, 4, 24, p, None, 0, p, 96, None) == ARG
+    assert wa(p, 288, None, 4, 4, 24, p, None, 0, p, 96, None) == ARG
+    assert wa(p, 288, p, 4, 4, 24, None, None, 0, p, 96, None) == ARG
+    assert wa(p, 288, p, 4, 4, 24, p, None, 0, None, 96, None) == ARG
+    assert wa(p, 288, p, 4, 4, 24, p, p, 0, p, 96, None) == ARG          # a mask with no windows in it
+    assert wa(p, 288, p, 4, 4, 33, p, None, 0, p, 132, None) == SHAPE    # d > 32
+    assert wa(p, 288, p, 4, 4, 0, p, None, 0, p, 96, None) == SHAPE
+    assert wa(p, 288, p, 4, 0, 24, p, None, 0, p, 96, None) == SHAPE
+    assert wa(p, 288, p, 0, 4, 24, p, None, 0, p, 96, None) == SHAPE
+    assert wa(p, 287, p, 4, 4, 24, p, None, 0, p, 96, None) == SHAPE     # ld_qkv < 3 * heads * d
+    assert wa(p, 288, p, 4, 4, 24, p, None, 0, p, 95, None) == SHAPE     # ldo < heads * d
+    # c2d_htsat_mel_patches(mel, b, t, bn_scale, bn_shift, out, stream): 2 <= t <= 1024, b >= 1
+    mp = L.c2d_htsat_mel_patches
+    assert mp(None, 1, 1001, p, p, p, None) == ARG
+    assert mp(p, 1, 1001, None, p, p, None) == ARG
+    assert mp(p, 1, 1001, p, None, p, None) == ARG
+    assert mp(p, 1, 1001, p, p, None, None) == ARG
+    assert mp(p, 1, 1, p, p, p, None) == SHAPE
+    assert mp(p, 1, 1025, p, p, p, None) == SHAPE
+    assert mp(p, 0, 1001, p, p, p, None) == SHAPE
+    # c2d_patch_merge_gather(x, b, h, w, c, out, stream)
+    pm = L.c2d_patch_merge_gather
+    assert pm(None, 2, 4, 4, 96, p, None) == ARG
+    assert pm(p, 2, 4, 4, 96, None, None) == ARG
+    for b, h, w, c in ((0, 4, 4, 96), (-1, 4, 4, 96), (2, 0, 4, 96), (2, 4, 0, 96), (2, 4, 4, 0), (2, 4, 4, -8),
+                       (2, 3, 4, 96), (2, 4, 5, 96), (2, 4, 4, 100)):
+        assert pm(p, b, h, w, c, p, None) == SHAPE, (b, h, w, c)
+    assert pm(odd, 2, 4, 4, 96, p, None) == ALIGN
+    assert pm(p, 2, 4, 4, 96, odd, None) == ALIGN
+    # c2d_row_mean(x, b, rows, c, ld, out, stream): rows = 0 has no mean
+    rm = L.c2d_row_mean
+    assert rm(None, 2, 64, 768, 768, p, None) == ARG
+    assert rm(p, 2, 64, 768, 768, None, None) == ARG
+    for b, rows, c, ld in ((2, 0, 768, 768), (2, -1, 768, 768), (0, 64, 768, 768), (2, 64, 0, 768),
+                           (2, 64, 768, 767)):
+        assert rm(p, b, rows, c, ld, p, None) == SHAPE, (b, rows, c, ld)
+    # c2d_l2_normalize(x, m, c, stream): m = 0 would be a zero-sized launch
+    l2 = L.c2d_l2_normalize
+    assert l2(None, 2, 512, None) == ARG
+    assert l2(p, 0, 512, None) == SHAPE
+    assert l2(p, -1, 512, None) == SHAPE
+    assert l2(p, 2, 0, None) == SHAPE
+    # c2d_latent_to_nhwc(x, n, c, hw, cpad, dup, out, stream)
+    ln = L.c2d_latent_to_nhwc
+    assert ln(None, 1, 4, 4096, 8, 1, p, None) == ARG
+    assert ln(p, 1, 4, 4096, 8, 1, None, None) == ARG
+    for n, c, hw, cpad in ((0, 4, 4096, 8), (1, 0, 4096, 8), (1, -4, 4096, 8), (1, 4, 0, 8), (1, 4, -1, 8),
+                           (1, 4, 4096, 3)):
+        assert ln(p, n, c, hw, cpad, 0, p, None) == SHAPE, (n, c, hw, cpad)
+    # c2d_add(a, b, out, n, stream): n % 8, 16-byte pointers; n = 0 is an empty sum -> OK
+    add = L.c2d_add
+    assert add(None, p, p, 8, None) == ARG
+    assert add(p, None, p, 8, None) == ARG
+    assert add(p, p, None, 8, None) == ARG
+    assert add(p, p, p, 12, None) == SHAPE
+    assert add(odd, p, p, 8, None) == ALIGN
+    assert add(p, odd, p, 8, None) == ALIGN
+    assert add(p, p, odd, 8, None) == ALIGN
+    assert add(p, p, p, 0, None) == OK

@@ -1,0 +1,395 @@
+"""The HTSAT audio tower on the GPU, kernel by kernel and block by block.
+
+Part 1: each of the tower's own kernels (and the small elementwise ones beside them) against a few lines
+of float64 torch on the CPU, fed the very fp16 / fp32 values the kernel reads.  Outputs are pre-filled
+with a sentinel and sit between guard bands; whatever lies outside the logical output must keep it.
+Part 2: htsat.SwinBlock against oracle.htsat_ref.swin_block, and the wired HTSATEncoder stage by stage
+against the oracle's loop, at tolerances that come from the CPU emulation in tests/htsat_parity.py.
+Every test records the figure it measured through tests/parity_log.
+"""
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import oracle.htsat_ref as R
+from clap2diffusion_amd import ops
+from clap2diffusion_amd.htsat import HTSATEncoder, _rel_index, _row_map, _shift_mask
+from clap2diffusion_amd.weights import synth_htsat
+from tests import htsat_parity as P
+from tests import parity_log
+
+pytestmark = pytest.mark.gpu
+
+U32 = 2.0 ** -24                    # fp32 unit roundoff
+PAD = 64                            # guard elements on either side of an output
+S16, S32 = -777.0, -7.77e7          # sentinels (exact in fp16 / fp32)
+
+
+class Guarded:
+    """A tensor of `shape` inside a sentinel-filled buffer, PAD elements of guard on either side."""
+
+    def __init__(self, dev, shape, dtype):
+        self.s = S16 if dtype == torch.float16 else S32
+        n = math.prod(shape)
+        self.buf = torch.full((n + 2 * PAD,), self.s, dtype=dtype, device=dev)
+        self.t = self.buf[PAD:PAD + n].view(shape)
+
+    def guards_intact(self) -> bool:
+        return bool((self.buf[:PAD] == self.s).all() and (self.buf[-PAD:] == self.s).all())
+
+
+def ulp16(v: torch.Tensor) -> torch.Tensor:
+    """One fp16 ulp at |v| (float64 in, float64 out; the subnormal spacing 2^-24 below 2^-14)."""
+    e = torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -14)))
+    return torch.pow(torch.tensor(2.0, dtype=torch.float64), e - 10)
+
+
+def bits(t: torch.Tensor) -> torch.Tensor:
+    return t.contiguous().view(torch.int16).cpu()
+
+
+# ---------------------------------------------------------------- window attention
+def wa_inputs(heads, d, nw, n_mask, seed, qk_scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    rows, c = nw * 64, heads * d
+    qkv = torch.randn(rows, 3 * c, generator=g)
+    qkv[:, :2 * c] *= qk_scale
+    row_map = torch.randperm(rows, generator=g).int()                 # arbitrary, not a Swin map
+    bias = torch.randn(heads, 64, 64, generator=g)
+    mask = None
+    if n_mask:
+        mask = torch.where(torch.rand(n_mask, 64, 64, generator=g) < 0.3, -100.0, 0.0)
+        t = torch.arange(64)
+        for m in range(n_mask):
+            mask[m, t, (7 * t + m) % 64] = 0.0                        # every query keeps a key
+    return qkv.half(), row_map, bias, mask
+
+
+def wa_reference(qkv, row_map, nw, heads, d, bias, mask):
+    """float64: gather by row_map, softmax(q k^T / sqrt(d) + bias[h] + mask[w % n_mask]) v, scatter back.
+    Also max|V| and L = the largest sum_i |q_i k_i| / sqrt(d) + |bias| over the unmasked logits."""
+    rows, c = nw * 64, heads * d
+    rm = row_map.long()
+    g = qkv.double()[rm].view(nw, 64, 3, heads, d)
+    q, k, v = (g[:, :, i].transpose(1, 2) for i in range(3))           # [nw, heads, 64, d]
+    s = q @ k.transpose(-1, -2) / math.sqrt(d) + bias.double()[None]
+    mag = q.abs() @ k.abs().transpose(-1, -2) / math.sqrt(d) + bias.double().abs()[None]
+    if mask is not None:
+        m = mask.double()[torch.arange(nw) % mask.shape[0]][:, None]
+        s = s + m
+        mag = torch.where(m < 0, torch.zeros_like(mag), mag)
+    o = s.softmax(-1) @ v
+    out = torch.zeros(rows, c, dtype=torch.float64)
+    out[rm] = o.transpose(1, 2).reshape(rows, c)
+    return out, v.abs().max().item(), mag.max().item()
+
+
+def wa_tolerance(vmax: float, big_l: float, d: int, masked: bool) -> float:
+    """|out - ref| bound.  out_i = sum_j p_j v_ji with p a convex weight vector, stored as fp16.
+      storage   one fp16 ulp at max|V| (|out| <= max|V|)
+      sums      the 64-term fp32 fma chain of p_j v_j, the 64-term sum l of the p_j and the product with
+                1 / l: (64 + 64 + 2) u max|V|, u = 2^-24
+      weights   a logit is d fmas of q k (q pre-scaled: one more rounding) plus bias and mask adds, each
+                rounding at most u L with L the largest sum |q_i k_i| / sqrt(d) + |bias|: delta = (d + 3) u L
+                absolute, on the logit and on the row maximum alike (2 delta).  __expf(x) is
+                exp2(x log2 e): rounding x = s - max (|x| <= 2 L), rounding the product and the 1-ulp
+                hardware exp2 give (4 L + 2) u relative.  A relative error eps on every unnormalised weight moves
+                a convex combination by at most 2 eps max|V|.
+      masked    keys at -100 carry weight <= exp(-(100 - 2 L)), below 2^-24 here (asserted): they are
+                left out of L and cost 64 u max|V| at the most.
+    """
+    eps = 2 * (d + 3) * U32 * big_l + (4 * big_l + 2) * U32
+    ulp = 2.0 ** (math.floor(math.log2(vmax)) - 10)
+    if masked:
+        assert 100 - 2 * big_l > 17, big_l
+    return ulp + (130 + (64 if masked else 0)) * U32 * vmax + 2 * eps * vmax
+
+
+def run_window_attention(dev, heads, d, nw, n_mask, seed, qk_scale=1.0, wide=False):
+    qkv, row_map, bias, mask = wa_inputs(heads, d, nw, n_mask, seed, qk_scale)
+    rows, c = nw * 64, heads * d
+    ref, vmax, big_l = wa_reference(qkv, row_map, nw, heads, d, bias, mask)
+    if wide:   # column views of wider buffers: ld_qkv > 3 heads d, ldo > heads d
+        qbuf = torch.full((rows, 3 * c + 40), S16, dtype=torch.float16, device=dev)
+        qbuf[:, 16:16 + 3 * c] = qkv.to(dev)
+        q_dev = qbuf[:, 16:16 + 3 * c]
+        gd = Guarded(dev, (rows, c + 24), torch.float16)
+        out = gd.t[:, 8:8 + c]
+    else:
+        q_dev = qkv.to(dev)
+        gd = Guarded(dev, (rows, c), torch.float16)
+        out = gd.t
+    ops.window_attention(q_dev, row_map.to(dev), nw, heads, d, bias.to(dev), None if mask is None else mask.to(dev),
+                         out)
+    torch.cuda.synchronize()
+    assert gd.guards_intact()
+    if wide:
+        assert bool((gd.t[:, :8] == S16).all() and (gd.t[:, 8 + c:] == S16).all())
+        assert torch.equal(qbuf[:, 16:16 + 3 * c].cpu(), qkv)
+    tol = wa_tolerance(vmax, big_l, d, mask is not None)
+    err = (out.double().cpu() - ref).abs().max().item()
+    parity_log.record(max_abs=err, tol=tol, vmax=vmax, logit_mag=big_l)
+    assert err <= tol, (err, tol)
+    return err, tol
+
+
+@pytest.mark.parametrize("nw", [4, 8, 12])                             # n_windows / n_mask = 1, 2, 3 at n_mask = 4
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("heads,d", [(4, 24), (32, 24), (2, 32), (3, 8)])
+def test_window_attention_matches_float64(dev, heads, d, masked, nw):
+    run_window_attention(dev, heads, d, nw, 4 if masked else 0, seed=100 * heads + d + nw + masked)
+
+
+def test_window_attention_wide_leading_dimensions(dev):
+    run_window_attention(dev, 4, 24, 8, 4, seed=7, wide=True)
+
+
+def test_window_attention_large_logits(dev):
+    """q and k scaled by sqrt(10): logits reach about +-40, exp() of them overflows fp16 and, unshifted,
+    loses all accuracy in fp32 sums; the max subtraction keeps it exact.  No mask, so L is the logits' own."""
+    err, tol = run_window_attention(dev, 4, 24, 6, 0, seed=11, qk_scale=10 ** 0.5)
+    qkv, row_map, bias, _ = wa_inputs(4, 24, 6, 0, 11, 10 ** 0.5)
+    g = qkv.double()[row_map.long()].view(6, 64, 3, 4, 24)
+    s = g[:, :, 0].transpose(1, 2) @ g[:, :, 1].transpose(1, 2).transpose(-1, -2) / math.sqrt(24)
+    assert s.max() > 35 and s.min() < -35, (s.min(), s.max())
+
+
+# ---------------------------------------------------------------- mel patches
+# For T < 1024 the kernel computes its source index t * (T - 1) / 1023 in fp32, as torch's float32 bicubic
+# does: near index 1000 that index is only good to 6e-5, and on white-noise mels (neighbouring frames differ
+# by several units) the interpolated value moves with it.  MEL_BICUBIC_F32[T] is the largest
+# |float32 - float64| of torch's own F.interpolate(bicubic, align_corners=True) on these very inputs
+# (after the BatchNorm affine), measured on the CPU; the absolute term is twice that, because the kernel's
+# fp32 evaluation order (index, weights, four-tap sum, BatchNorm inside the taps) is not torch's.
+MEL_BICUBIC_F32 = {1023: 5.59e-4, 1001: 7.01e-4, 300: 3.50e-4, 37: 1.88e-5, 2: 5.67e-6}
+MEL_ABS = {t: 2 * v for t, v in MEL_BICUBIC_F32.items()}
+MEL_ABS[1024] = 0.0               # a copy: no resize
+
+
+def mel_inputs(t, b=2):
+    g = torch.Generator().manual_seed(5000 + t)
+    mel = torch.randn(b, t, 64, generator=g) * 2.0 - 4.0
+    scale = (0.5 + torch.rand(64, generator=g)) * torch.where(torch.arange(64) % 3 == 1, -1.0, 1.0)
+    shift = 0.5 * torch.randn(64, generator=g)
+    return mel, scale, shift
+
+
+def mel_reference(mel, scale, shift, dtype=torch.float64):
+    """BatchNorm affine, bicubic time resize to 1024, the mel-to-image fold of htsat_forward, 4x4 patches."""
+    b, t, f = mel.shape
+    x = mel.to(dtype) * scale.to(dtype) + shift.to(dtype)
+    if t < 1024:
+        x = F.interpolate(x[:, None], (1024, f), mode="bicubic", align_corners=True)[:, 0]
+    img = x.reshape(b, 4, 256, f).permute(0, 1, 3, 2).reshape(b, 1, 4 * f, 256)
+    return F.unfold(img, 4, stride=4).transpose(1, 2).reshape(b * 4096, 16)
+
+
+@pytest.mark.parametrize("t", [1024, 1023, 1001, 300, 37, 2])
+def test_mel_patches_match_float64(dev, t):
+    mel, scale, shift = mel_inputs(t)
+    ref = mel_reference(mel, scale, shift)
+    out = ops.htsat_mel_patches(mel.to(dev), scale.to(dev), shift.to(dev))
+    gd = Guarded(dev, (2 * 4096, 64), torch.float16)
+    torch.ops.c2d.htsat_mel_patches(mel.to(dev), scale.to(dev), shift.to(dev), gd.t)
+    torch.cuda.synchronize()
+    assert gd.guards_intact() and torch.equal(bits(gd.t), bits(out))
+    out = out.cpu()
+    assert out.shape == (2 * 4096, 64) and not out[:, 16:].view(torch.int16).any()      # exactly +0
+    diff = (out[:, :16].double() - ref).abs()
+    # T = 1024 is a copy: the float64 value rounded to fp16, within one fp16 ulp.  T < 1024 adds MEL_ABS[T].
+    tol = ulp16(ref) + MEL_ABS[t]
+    parity_log.record(max_abs=diff.max().item(), worst_over_tol=(diff / tol).max().item(), 
+                      abs_term=MEL_ABS[t])
+    assert bool((diff <= tol).all()), (diff / tol).max().item()
+
+
+# ---------------------------------------------------------------- bit-exact movers
+@pytest.mark.parametrize("b,h,w,c", [(2, 4, 4, 96), (1, 8, 4, 192), (3, 2, 2, 8)])
+def test_patch_merge_gather_bit_exact(dev, b, h, w, c):
+    n = b * h * w * c
+    x = torch.arange(n, dtype=torch.int16).view(torch.float16).view(b * h * w, c)       # distinct bit patterns, no NaN
+    assert n < 0x7C00
+    xr = x.view(b, h, w, c)
+    ref = torch.cat([xr[:, r::2, cc::2, :] for cc in range(2) for r in range(2)], dim=-1).reshape(-1, 4 * c)
+    out = ops.patch_merge_gather(x.to(dev), b, h, w, c)
+    gd = Guarded(dev, (b * (h // 2) * (w // 2), 4 * c), torch.float16)
+    torch.ops.c2d.patch_merge_gather(x.to(dev), b, h, w, c, gd.t)
+    torch.cuda.synchronize()
+    assert gd.guards_intact() and out.shape == ref.shape
+    wrong = int((bits(out) != bits(ref)).sum()) + int((bits(gd.t) != bits(ref)).sum())
+    parity_log.record(mismatched=wrong)
+    assert wrong == 0
+
+
+@pytest.mark.parametrize("n,alias", [(8, False), (8 * 257, False), (8 * 257, True), (8 * (4096 * 256 + 3), False)])
+def test_add_bit_exact(dev, n, alias):
+    """The last size is one 8-element chunk stride past the 4096-block x 256-thread grid cap.  The sum of two
+    unit-scale fp16 values is exact in float64 (and in fp32), so .half() rounds it once."""
+    g = torch.Generator().manual_seed(n)
+    a, b = torch.randn(n, generator=g).half(), torch.randn(n, generator=g).half()
+    ref = (a.double() + b.double()).half()
+    ga = Guarded(dev, (n,), torch.float16)
+    ga.t.copy_(a)
+    if alias:
+        out = ops.add(ga.t, b.to(dev), out=ga.t)
+        gd = ga
+    else:
+        gd = Guarded(dev, (n,), torch.float16)
+        out = ops.add(ga.t, b.to(dev), out=gd.t)
+        assert torch.equal(bits(ops.add(ga.t, b.to(dev))), bits(ref))          # the allocating form
+        assert torch.equal(bits(ga.t), bits(a))
+    torch.cuda.synchronize()
+    assert gd.guards_intact() and ga.guards_intact()
+    wrong = int((bits(out) != bits(ref)).sum())
+    parity_log.record(mismatched=wrong)
+    assert wrong == 0
+
+
+@pytest.mark.parametrize("h,w", [(1, 1), (15, 17)])
+@pytest.mark.parametrize("dup", [False, True])
+def test_latent_to_nhwc_bit_exact(dev, dup, h, w):
+    n, c, cpad = 2, 4, 8
+    x = torch.randn(n, c, h, w, generator=torch.Generator().manual_seed(h * w + dup))
+    ref = torch.zeros(n, h, w, cpad, dtype=torch.float16)
+    ref[..., :c] = x.permute(0, 2, 3, 1).half()
+    if dup:
+        ref = torch.cat([ref, ref])
+    out = ops.latent_to_nhwc(x.to(dev), cpad, dup)
+    gd = Guarded(dev, tuple(ref.shape), torch.float16)
+    torch.ops.c2d.latent_to_nhwc(x.to(dev), cpad, dup, gd.t)
+    torch.cuda.synchronize()
+    assert gd.guards_intact() and out.shape == ref.shape
+    assert not bits(out)[..., c:].any()                                            # pad channels exactly +0
+    if dup:
+        assert torch.equal(bits(out[n:]), bits(out[:n]))
+    wrong = int((bits(out) != bits(ref)).sum()) + int((bits(gd.t) != bits(ref)).sum())
+    parity_log.record(mismatched=wrong)
+    assert wrong == 0
+
+
+# ---------------------------------------------------------------- row mean, L2 normalise
+@pytest.mark.parametrize("view", [False, True])
+@pytest.mark.parametrize("c", [8, 768])
+@pytest.mark.parametrize("rows", [1, 64, 100])
+def test_row_mean_matches_float64(dev, rows, c, view):
+    """fp32 serial sum s_r = fl(s_{r-1} + x_r) of exact fp16 inputs, then one division: |mean - exact| <=
+    (rows - 1) u sum|x| / rows + u |mean| <= rows u mean|x| per column (u = 2^-24)."""
+    b = 3
+    x = (torch.randn(b * rows, c, generator=torch.Generator().manual_seed(rows + c)) * 2 + 0.5).half()
+    if view:   # a column view: ld = c + 24 > c
+        buf = torch.full((b * rows, c + 24), S16, dtype=torch.float16, device=dev)
+        buf[:, 8:8 + c] = x.to(dev)
+        xd = buf[:, 8:8 + c]
+    else:
+        xd = x.to(dev)
+    out = ops.row_mean(xd, b, rows)
+    gd = Guarded(dev, (b, c), torch.float32)
+    torch.ops.c2d.row_mean(xd, b, rows, gd.t)
+    torch.cuda.synchronize()
+    assert gd.guards_intact() and out.shape == (b, c) and out.dtype == torch.float32
+    assert torch.equal(gd.t.cpu(), out.cpu())
+    xr = x.double().view(b, rows, c)
+    ref, tol = xr.mean(1), rows * U32 * xr.abs().mean(1)
+    diff = (out.double().cpu() - ref).abs()
+    parity_log.record(max_abs=diff.max().item(), worst_over_tol=(diff / tol).max().item())
+    assert bool((diff <= tol).all()), (diff / tol).max().item()
+
+
+@pytest.mark.parametrize("c", [1, 63, 512, 1000])
+def test_l2_normalize_matches_float64(dev, c):
+    """F.normalize divides by max(||x||_2, 1e-12).  So an all-zero row stays zero; a row of magnitude 1e-20 has
+    a norm below 1e-12 and comes out as x * 1e12 (about 1e-8, not unit length); a row of magnitude 1e15 is
+    normalised as usual.  The kernel's fp32 sum of squares underflows on the 1e-20 row, which changes
+    nothing (the clamp decides), and at 1e15 it is c * 1e30 <= 1e33, well inside fp32.  It would overflow
+    only past |x| ~ 1e19 / sqrt(c); the product hands it the fp16 outputs of linear2 (|x| <= 65504), so
+    that range is unreachable and the kernel stays as it is: nothing is narrowed here.
+    Bound: squares and the per-thread serial sum (ceil(c / 256) terms), the 6-step wave reduction and the
+    4 partial sums each cost u relative on the all-positive sum; sqrt halves that; 1e-12f, the reciprocal
+    and the product add 3 u: below (ceil(c / 256) + 16) u relative, u = 2^-24."""
+    g = torch.Generator().manual_seed(c)
+    x = torch.randn(6, c, generator=g)
+    x[3] = 0.0
+    x[4] *= 1e-20
+    x[5] *= 1e15
+    ref = F.normalize(x.double(), dim=-1)
+    assert not ref[3].any() and (ref[4] - x[4].double() * 1e12).abs().max() <= 1e-20 and ref[5].norm() > 0.999999
+    gd = Guarded(dev, (6, c), torch.float32)
+    gd.t.copy_(x)
+    out = ops.l2_normalize_(gd.t)
+    torch.cuda.synchronize()
+    assert out.data_ptr() == gd.t.data_ptr() and gd.guards_intact()
+    out = out.cpu()
+    assert bool(torch.isfinite(out).all()) and not out[3].any()
+    tol = (math.ceil(c / 256) + 16) * U32 * ref.abs()
+    diff = (out.double() - ref).abs()
+    worst = (diff / tol.clamp_min(1e-300)).max().item()
+    parity_log.record(max_abs=diff.max().item(), worst_over_tol=worst)
+    assert bool((diff <= tol).all()), worst
+
+
+# ---------------------------------------------------------------- Swin block
+@pytest.mark.parametrize("case", P.BLOCK_CASES, ids=P.case_id)
+def test_swin_block_matches_oracle(dev, case):
+    c, heads, grid, shift, b = case
+    sd, x = P.block_state_dict(c, heads, 0), P.block_input(c, grid, b, 0)
+    with torch.no_grad():
+        ref = R.swin_block(x, sd, P.BLOCK_KEY, b, grid, grid, c, heads, shift)
+    enc = HTSATEncoder(P.block_cfg(c, heads)).to(dev)
+    enc.load_clap_state_dict(sd)
+    blk = enc.stages[0][0]
+    assert _rel_index(8).shape == (64, 64)
+    row_map = torch.from_numpy(_row_map(b, grid, grid, 8, shift)).to(dev)
+    mask = torch.from_numpy(_shift_mask(grid, grid, 8, shift)).to(dev) if shift else None
+    xin = x.reshape(b * grid * grid, c).half().to(dev)
+    with torch.no_grad():
+        out = blk(xin.clone(), row_map, mask, b * (grid // 8) ** 2)      # the block overwrites its input
+    l2, win = P.block_metrics(out.float().cpu(), ref, b, grid, shift)
+    tol_l2, tol_win = P.BLOCK_TOL[case]
+    parity_log.record(rel_l2=l2, win_rel_l2=win, tol_l2=tol_l2, tol_win=tol_win)
+    assert l2 <= tol_l2 and win <= tol_win, (l2, tol_l2, win, tol_win)
+
+
+# ---------------------------------------------------------------- the wired tower, stage by stage
+@pytest.fixture(scope="module")
+def tower(dev):
+    enc = HTSATEncoder().to(dev)
+    enc.load_clap_state_dict(synth_htsat(0))
+    return enc, P.round_linear_weights(synth_htsat(0))
+
+
+@pytest.mark.parametrize("t", P.TOWER_T)
+def test_tower_stages_match_oracle(dev, tower, monkeypatch, t):
+    """The real HTSATEncoder (its own _window_tables: alternating shift, none at h = 8, nw) against the
+    oracle's loop rebuilt from swin_block and patch_merge, at each stage's last block, the pooled vector
+    and the embedding.  T = 1001: the stage points only (test_hip_htsat_matches_transformers has the end)."""
+    enc, sd = tower
+    b = 2
+    mel = P.golden_mel(t, b, P.TOWER_MEL_SEED[t])
+    with torch.no_grad():
+        ref = P.tower_points(sd, mel)
+    got, hooks = {}, []
+    for i, stage in enumerate(enc.stages):
+        hooks.append(stage[-1].register_forward_hook(
+            lambda m, a, o, i=i: got.__setitem__(f"stage{i}", o.float().cpu().view(b, -1, o.shape[-1]))))
+    real_mean = ops.row_mean
+
+    def row_mean(*a):
+        got["pooled"] = real_mean(*a)
+        return got["pooled"]
+    monkeypatch.setattr(ops, "row_mean", row_mean)
+    try:
+        got["embedding"] = enc(mel.to(dev)).cpu()
+    finally:
+        for h in hooks:
+            h.remove()
+    got["pooled"] = got["pooled"].cpu()
+    m = P.tower_metrics(got, ref, b)
+    tol = P.TOWER_TOL[t]
+    n = 4 if t == 1001 else 6
+    parity_log.record(**{p: v for p, v in zip(P.TOWER_POINTS[:n], m)},
+                      **{"tol_" + p: v for p, v in zip(P.TOWER_POINTS[:n], tol)})
+    for p, v, tl in list(zip(P.TOWER_POINTS, m, tol))[:n]:
+        assert v <= tl, (p, v, tl, m)
+
