@@ -240,6 +240,65 @@ __global__ void vae_posterior_noise_kernel(const f16* __restrict__ mom, int ld, 
     x[i] = z;
 }
 
+// The inpainting step's last launch: cfg_ddim_kernel's update (the same roundings, so a pixel with mask 1 gets
+// that kernel's bits) blended with the original re-noised to the next step's timestep, or the original
+// itself at the last step.  One thread per (image, latent pixel): one 8-byte load each of the uncond and cond
+// eps pixel, one mask load, four channel updates (each channel's accesses to x / z0 / noise are coalesced).
+// x is read and written in place, so it carries no __restrict__.
+__global__ void cfg_ddim_masked_kernel(const f16x4* __restrict__ eps, float* x, const float* __restrict__ z0,
+                                       const float* __restrict__ noise, const float* __restrict__ mask, int b, int hw,
+                                       int steps, float gsc, const float* __restrict__ coef,
+                                       const int* __restrict__ step_index) {
+    // cfg_ddim_kernel's source expressions leave the compiler free to fuse multiply-adds, and the same source
+    // fuses differently inside this kernel.  So contraction is off and the roundings are spelled out as that
+    // kernel's ISA performs them: e and x - sqrt(1 - a_t) e each one fused multiply-add, the final sum two
+    // rounded products and an add.  The pairing is pinned by tests/test_inpaint_gpu.py (mask 1 must give
+    // c2d_cfg_ddim_step's bits): if a compiler upgrade breaks that test, re-derive this sequence from
+    // cfg_ddim_kernel's ISA.
+#pragma clang fp contract(off)
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)b * hw) return;
+    const int st = *step_index;
+    if ((unsigned)st >= (unsigned)steps) return;   // a counter outside the table: nothing is read or written
+    const size_t bi = i / hw, p = i - bi * hw;
+    const float a_t = coef[st * 2], a_p = coef[st * 2 + 1];
+    const bool last = st == steps - 1;
+    const f16x4 vu = eps[i], vc = eps[(size_t)b * hw + i];
+    const float m = mask[i];
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch) {
+        const size_t j = (bi * 4 + ch) * hw + p;
+        const float eu = (float)vu[ch];
+        const float ec = (float)vc[ch];
+        const float e = fmaf(gsc, ec - eu, eu);
+        const float x0 = fmaf(-sqrtf(1.0f - a_t), e, x[j]) / sqrtf(a_t);
+        const float xn = sqrtf(a_p) * x0 + sqrtf(1.0f - a_p) * e;
+        const float z = z0[j];
+        const float known = last ? z : sqrtf(a_p) * z + sqrtf(1.0f - a_p) * noise[j];
+        x[j] = (1.0f - m) * known + m * xn;
+    }
+}
+
+// uint8 mask [n][8h][8w] -> fp32 [n][h][w]: the sample at (8y, 8x) (F.interpolate nearest at an exact factor 8),
+// binarised at 128
+__global__ void mask_to_latent_kernel(const uint8_t* __restrict__ mask, int n, int h, int w, float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n * h * w) return;
+    const size_t xo = i % w, yo = (i / w) % h, bi = i / ((size_t)w * h);
+    out[i] = mask[(bi * 8 * h + 8 * yo) * 8 * w + 8 * xo] >= 128 ? 1.0f : 0.0f;
+}
+
+// out pixel = mask >= 128 ? decoded : original, uint8 RGB; each thread reads its pixel of both images before it
+// writes, so out may be decoded (no __restrict__ on either)
+__global__ void composite_u8_kernel(const uint8_t* decoded, const uint8_t* __restrict__ original,
+                                    const uint8_t* __restrict__ mask, size_t npix, uint8_t* out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const bool repaint = mask[i] >= 128;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[i * 3 + c] = repaint ? decoded[i * 3 + c] : original[i * 3 + c];
+}
+
 }  // namespace c2d
 
 using namespace c2d;
@@ -287,6 +346,40 @@ extern "C" int c2d_vae_posterior_noise(const void* moments, int ld, const float*
     const size_t tot = (size_t)n * 4 * hw;
     hipLaunchKernelGGL(vae_posterior_noise_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, (const f16*)moments, ld, eps, noise, coef, step_index, n, hw, scaling, x);
+    return check_launch();
+}
+
+extern "C" int c2d_cfg_ddim_step_masked(const void* eps, float* x, const float* z0, const float* noise,
+                                        const float* mask, int b, int hw, int steps, float guidance,
+                                        const float* coef, int* step_index, int advance, void* stream) {
+    if (!eps || !x || !z0 || !noise || !mask || !coef || !step_index) return C2D_E_ARG;
+    if (b <= 0 || hw <= 0 || steps <= 0) return C2D_E_SHAPE;
+    if (((uintptr_t)eps & 7) || (((uintptr_t)x | (uintptr_t)z0 | (uintptr_t)noise | (uintptr_t)mask) & 3))
+        return C2D_E_ALIGN;
+    const size_t tot = (size_t)b * hw;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(cfg_ddim_masked_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s,
+                       (const f16x4*)eps, x, z0, noise, mask, b, hw, steps, guidance, coef, step_index);
+    if (advance) hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, step_index);
+    return check_launch();
+}
+
+extern "C" int c2d_mask_to_latent(const uint8_t* mask_u8, int n, int h, int w, float* out, void* stream) {
+    if (!mask_u8 || !out) return C2D_E_ARG;
+    if (n <= 0 || h <= 0 || w <= 0) return C2D_E_SHAPE;
+    if ((uintptr_t)out & 3) return C2D_E_ALIGN;
+    const size_t tot = (size_t)n * h * w;
+    hipLaunchKernelGGL(mask_to_latent_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       mask_u8, n, h, w, out);
+    return check_launch();
+}
+
+extern "C" int c2d_composite_u8(const uint8_t* decoded, const uint8_t* original, const uint8_t* mask_u8, size_t npix,
+                                uint8_t* out, void* stream) {
+    if (!decoded || !original || !mask_u8 || !out) return C2D_E_ARG;
+    if (npix == 0 || npix > (size_t)INT32_MAX) return C2D_E_SHAPE;   // a negative count cast to size_t lands above
+    hipLaunchKernelGGL(composite_u8_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       decoded, original, mask_u8, npix, out);
     return check_launch();
 }
 

@@ -529,6 +529,56 @@ def vae_posterior_noise(moments: torch.Tensor, out: torch.Tensor, scaling: float
     return out
 
 
+def cfg_ddim_step_masked(eps: torch.Tensor, x: torch.Tensor, z0: torch.Tensor, noise: torch.Tensor, mask: torch.Tensor,
+                         guidance: float, coef: torch.Tensor, step_index: torch.Tensor,
+                         advance: bool = True) -> torch.Tensor:
+    """The inpainting step's update of x fp32 [B, 4, h, w] in place (c2d::cfg_ddim_step_masked): cfg_ddim_step's
+    result where mask fp32 [B, h, w] is 1, the original z0 re-noised with `noise` to the next step's timestep
+    (z0 itself at the last step) where it is 0, the blend in between."""
+    _require(x, "x")
+    assert eps.dtype == F16 and eps.is_contiguous() and eps.numel() == 2 * x.numel()
+    assert x.dim() == 4 and x.shape[1] == 4
+    for t in (x, z0, noise):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape and t.is_cuda
+    assert mask.dtype == torch.float32 and mask.is_contiguous() and mask.is_cuda
+    assert tuple(mask.shape) == (x.shape[0], x.shape[2], x.shape[3])
+    assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.dim() == 2 and coef.shape[1] == 2
+    assert step_index.dtype == torch.int32
+    C2D.cfg_ddim_step_masked(eps, x, z0, noise, mask, float(guidance), coef, step_index, bool(advance))
+    return x
+
+
+def mask_to_latent(mask_u8: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """uint8 [N, H, W] (H, W multiples of 8; >= 128 = repaint) -> fp32 [N, H/8, W/8] of 0 / 1: the sample at
+    (8y, 8x), i.e. the binarised mask under F.interpolate nearest (c2d::mask_to_latent)."""
+    _require(mask_u8, "mask_u8")
+    assert mask_u8.dtype == torch.uint8 and mask_u8.dim() == 3 and mask_u8.is_contiguous()
+    n, hgt, wid = mask_u8.shape
+    assert hgt % 8 == 0 and wid % 8 == 0 and hgt > 0 and wid > 0, f"mask size {hgt}x{wid} is no multiple of 8"
+    if out is None:
+        out = torch.empty((n, hgt // 8, wid // 8), device=mask_u8.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, hgt // 8, wid // 8)
+    C2D.mask_to_latent(mask_u8, out)
+    return out
+
+
+def composite_u8(decoded: torch.Tensor, original: torch.Tensor, mask_u8: torch.Tensor,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """uint8 images [N, H, W, 3] and mask [N, H, W] -> mask >= 128 ? decoded : original (c2d::composite_u8); out may
+    be decoded."""
+    _require(decoded, "decoded")
+    for t in (decoded, original):
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda and t.shape == decoded.shape
+    assert decoded.dim() == 4 and decoded.shape[-1] == 3
+    assert mask_u8.dtype == torch.uint8 and mask_u8.is_contiguous() and mask_u8.is_cuda
+    assert mask_u8.shape == decoded.shape[:-1]
+    if out is None:
+        out = torch.empty_like(decoded)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == decoded.shape
+    C2D.composite_u8(decoded, original, mask_u8, out)
+    return out
+
+
 def upsample_nearest2x(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """NHWC fp16 nearest x2 (diffusers Upsample2D interpolate step)."""
     n, h, w, c = x.shape

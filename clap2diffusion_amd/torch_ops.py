@@ -292,6 +292,31 @@ def vae_posterior_noise(moments: Tensor, eps: Optional[Tensor], noise: Optional[
           "c2d_vae_posterior_noise")
 
 
+@custom_op("c2d::cfg_ddim_step_masked", mutates_args=("x", "step_index"), device_types=_CU)
+def cfg_ddim_step_masked(eps: Tensor, x: Tensor, z0: Tensor, noise: Tensor, mask: Tensor, guidance: float,
+                         coef: Tensor, step_index: Tensor, advance: bool) -> None:
+    """c2d_cfg_ddim_step_masked: the CFG + DDIM update of x [b][4][h][w] blended with the known region (z0, noise
+    as x; mask fp32 [b][h][w]); the number of steps is coef's row count."""
+    b, _, hgt, wid = x.shape
+    check(lib().c2d_cfg_ddim_step_masked(ptr(eps), ptr(x), ptr(z0), ptr(noise), ptr(mask), b, hgt * wid,
+                                         coef.shape[0], guidance, ptr(coef), ptr(step_index), int(advance),
+                                         stream_ptr()), "c2d_cfg_ddim_step_masked")
+
+
+@custom_op("c2d::mask_to_latent", mutates_args=("out",), device_types=_CU)
+def mask_to_latent(mask_u8: Tensor, out: Tensor) -> None:
+    """c2d_mask_to_latent: uint8 [n][8h][8w] -> fp32 [n][h][w], 1 where the sample at (8y, 8x) is >= 128."""
+    n, h, w = out.shape
+    check(lib().c2d_mask_to_latent(ptr(mask_u8), n, h, w, ptr(out), stream_ptr()), "c2d_mask_to_latent")
+
+
+@custom_op("c2d::composite_u8", mutates_args=("out",), device_types=_CU)
+def composite_u8(decoded: Tensor, original: Tensor, mask_u8: Tensor, out: Tensor) -> None:
+    """c2d_composite_u8: out = mask_u8 >= 128 ? decoded : original over uint8 [n][h][w][3] images."""
+    check(lib().c2d_composite_u8(ptr(decoded), ptr(original), ptr(mask_u8), mask_u8.numel(), ptr(out), stream_ptr()),
+          "c2d_composite_u8")
+
+
 @custom_op("c2d::upsample_nearest2x", mutates_args=("out",), device_types=_CU)
 def upsample_nearest2x(x: Tensor, out: Tensor) -> None:
     n, h, w, c = x.shape
@@ -307,11 +332,12 @@ def add(a: Tensor, b: Tensor, out: Tensor) -> None:
 for _op in (pack_weights, groupnorm_stats, groupnorm_apply, groupnorm, groupnorm_pad, groupnorm_moments, layernorm_stats, layernorm, attention_fwd,
             attention_small, window_attention, htsat_mel_patches, patch_merge_gather, row_mean, softmax_rows,
             l2_normalize, clap_log_mel, timestep_embedding, cfg_ddim_step, latent_to_nhwc, upsample_nearest2x, add,
-            image_to_nhwc, vae_posterior_noise):
+            image_to_nhwc, vae_posterior_noise, cfg_ddim_step_masked, mask_to_latent, composite_u8):
     _op.register_fake(lambda *args, **kwargs: None)
 
 OPS = ("conv2d_igemm", "pack_weights", "groupnorm_stats", "groupnorm_apply", "groupnorm", "groupnorm_pad", "groupnorm_moments",
        "layernorm_stats",
        "layernorm", "attention_fwd", "attention_small", "window_attention", "htsat_mel_patches", "patch_merge_gather",
        "row_mean", "softmax_rows", "l2_normalize", "clap_log_mel", "timestep_embedding", "cfg_ddim_step",
-       "latent_to_nhwc", "upsample_nearest2x", "add", "image_to_nhwc", "vae_posterior_noise")
+       "latent_to_nhwc", "upsample_nearest2x", "add", "image_to_nhwc", "vae_posterior_noise",
+       "cfg_ddim_step_masked", "mask_to_latent", "composite_u8")

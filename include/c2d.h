@@ -479,6 +479,43 @@ int c2d_vae_posterior_noise(const void* moments, int ld, const float* eps, const
                             const float* coef, const int* step_index, int n, int hw, float scaling, float* x,
                             void* stream);
 
+/*
+ * Inpainting (three entry points added to the r7 ABI: no struct changed, c2d_version still answers "r7").
+ *
+ * The inpainting step's last launch: classifier-free guidance, the DDIM update and the blend with the known
+ * region in one kernel.  eps fp16 NHWC [2b][hw][4] (uncond rows first, 8-byte aligned), x fp32 NCHW [b][4][hw]
+ * in place, z0 (the scaled posterior sample or mode of the init image) and noise (the tensor that made the
+ * initial latents) fp32 NCHW [b][4][hw], mask fp32 [b][hw] (1 = repaint, 0 = keep; one value per latent pixel,
+ * broadcast over the four channels; fractions blend).  With st = *step_index, fp32 throughout:
+ *   x'    = the update of c2d_cfg_ddim_step (the same operations and roundings: where mask is 1 the result
+ *           has that kernel's bits)
+ *   known = z0                                          st == steps - 1
+ *           sqrt(a) z0 + sqrt(1 - a) noise, a = coef[2 st + 1]   otherwise
+ *   x     = (1 - mask) known + mask x'
+ * coef is c2d_cfg_ddim_step's [steps][2] table.  a is this step's alpha_prev, which under the scheduler's
+ * leading spacing is the next step's alpha_t, so known is DDIMScheduler.add_noise(z0, noise, timesteps[st + 1])
+ * and no row past the table is read.  A counter outside [0, steps) leaves x as it is.  advance as in
+ * c2d_cfg_ddim_step.  Replaces, for a 4-channel UNet, the per-step blend of diffusers 0.23.1
+ * StableDiffusionInpaintPipeline (init_latents_proper / init_mask).
+ * C2D_E_ARG: a null pointer; C2D_E_SHAPE: b, hw or steps <= 0; C2D_E_ALIGN: eps not 8-byte or an fp32 tensor
+ * not 4-byte aligned; all before any launch.
+ */
+int c2d_cfg_ddim_step_masked(const void* eps, float* x, const float* z0, const float* noise, const float* mask,
+                             int b, int hw, int steps, float guidance, const float* coef, int* step_index,
+                             int advance, void* stream);
+
+/* uint8 mask [n][8h][8w] -> fp32 latent mask [n][h][w]: out[y][x] = mask_u8[8y][8x] >= 128 ? 1 : 0, i.e. the
+ * inpaint pipeline's binarisation at 0.5 of mask / 255 followed by F.interpolate(size=(h, w)) (nearest).
+ * C2D_E_ARG: a null pointer; C2D_E_SHAPE: n, h or w <= 0; C2D_E_ALIGN: out not 4-byte aligned. */
+int c2d_mask_to_latent(const uint8_t* mask_u8, int n, int h, int w, float* out, void* stream);
+
+/* Pixel-space composite of an inpainting result: decoded, original, out uint8 [npix][3], mask_u8 [npix];
+ * out = mask_u8 >= 128 ? decoded : original, bit for bit.  out may be decoded; it must not overlap original
+ * or mask_u8.
+ * C2D_E_ARG: a null pointer; C2D_E_SHAPE: npix == 0 or npix > INT32_MAX. */
+int c2d_composite_u8(const uint8_t* decoded, const uint8_t* original, const uint8_t* mask_u8, size_t npix,
+                     uint8_t* out, void* stream);
+
 /* Nearest-neighbour x2 upsample of NHWC fp16 [n, h, w, c] -> [n, 2h, 2w, c], c % 8 == 0.
  * Replaces F.interpolate(scale_factor=2.0, mode="nearest") in diffusers Upsample2D
  * (the UNet up path and the VAE decoder). */
