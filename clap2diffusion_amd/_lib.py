@@ -28,6 +28,7 @@ EXPORTS = [
     "c2d_cfg_ddim_step", "c2d_latent_to_nhwc", "c2d_upsample_nearest2x", "c2d_add", "c2d_last_hip_error", "c2d_version",
     "c2d_image_to_nhwc", "c2d_vae_posterior_noise",
     "c2d_cfg_ddim_step_masked", "c2d_mask_to_latent", "c2d_composite_u8",
+    "c2d_inpaint_prepare",
 ]
 
 
@@ -98,6 +99,7 @@ def lib() -> ctypes.CDLL:
         "c2d_cfg_ddim_step_masked": ([vp, vp, vp, vp, vp, i, i, i, f, vp, vp, i, vp], i),
         "c2d_mask_to_latent": ([vp, i, i, i, vp, vp], i),
         "c2d_composite_u8": ([vp, vp, vp, sz, vp, vp], i),
+        "c2d_inpaint_prepare": ([vp, i, vp, vp, vp, vp, vp, i, i, i, i, f, vp, vp, vp, vp], i),
         "c2d_add": ([vp, vp, vp, sz, vp], i),
         "c2d_last_hip_error": ([], i),
         "c2d_version": ([], ctypes.c_char_p),

@@ -299,6 +299,45 @@ __global__ void composite_u8_kernel(const uint8_t* decoded, const uint8_t* __res
     for (int c = 0; c < 3; ++c) out[i * 3 + c] = repaint ? decoded[i * 3 + c] : original[i * 3 + c];
 }
 
+// The entry into the inpainting loop in one launch: vae_posterior_noise_kernel's z0 (kept, the masked step blends
+// with it), the loop's first latents x (z0 noised to the step the device counter names, or the noise itself
+// when the loop starts from pure noise) and mask_to_latent_kernel's mask.  One thread per (image, latent pixel):
+// its 8 moments are the first 16 bytes of its row; the four channel accesses to eps / noise / z0 / x are each
+// coalesced across the wave (consecutive lanes, consecutive pixels of one channel plane), as in
+// cfg_ddim_masked_kernel.  The outputs are __restrict__: x must not alias noise or z0 (c2d.h).
+__global__ void inpaint_prepare_kernel(const f16* __restrict__ mom, int ld, const float* __restrict__ eps,
+                                       const float* __restrict__ noise, const uint8_t* __restrict__ mask_u8,
+                                       const float* __restrict__ coef, const int* __restrict__ step_index,
+                                       int pure_noise, int n, int h, int w, float scaling, float* __restrict__ z0,
+                                       float* __restrict__ x, float* __restrict__ mask) {
+    const size_t hw = (size_t)h * w;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n * hw) return;
+    const size_t bi = i / hw, p = i - bi * hw;
+    const size_t yo = p / w, xo = p - yo * w;
+    float sa = 0.0f, sn = 1.0f;
+    if (!pure_noise) {
+        const float a = coef[2 * (*step_index)];
+        sa = sqrtf(a);
+        sn = sqrtf(1.0f - a);
+    }
+    const f16* row = mom + i * ld;
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch) {
+        const size_t j = (bi * 4 + ch) * hw + p;
+        float z = (float)row[ch];
+        if (eps) {
+            const float lv = fminf(fmaxf((float)row[4 + ch], -30.0f), 20.0f);
+            z += expf(0.5f * lv) * eps[j];
+        }
+        z *= scaling;
+        const float nz = noise[j];
+        z0[j] = z;
+        x[j] = pure_noise ? nz : sa * z + sn * nz;
+    }
+    mask[i] = mask_u8[(bi * 8 * h + 8 * yo) * 8 * w + 8 * xo] >= 128 ? 1.0f : 0.0f;
+}
+
 }  // namespace c2d
 
 using namespace c2d;
@@ -380,6 +419,23 @@ extern "C" int c2d_composite_u8(const uint8_t* decoded, const uint8_t* original,
     if (npix == 0 || npix > (size_t)INT32_MAX) return C2D_E_SHAPE;   // a negative count cast to size_t lands above
     hipLaunchKernelGGL(composite_u8_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        decoded, original, mask_u8, npix, out);
+    return check_launch();
+}
+
+extern "C" int c2d_inpaint_prepare(const void* moments, int ld, const float* eps, const float* noise,
+                                   const uint8_t* mask_u8, const float* coef, const int* step_index, int pure_noise,
+                                   int n, int h, int w, float scaling, float* z0, float* x, float* mask,
+                                   void* stream) {
+    if (!moments || !noise || !mask_u8 || !z0 || !x || !mask || (!pure_noise && (!coef || !step_index)))
+        return C2D_E_ARG;
+    if (n <= 0 || h <= 0 || w <= 0 || ld < 8) return C2D_E_SHAPE;
+    if (((uintptr_t)moments & 1) || (((uintptr_t)eps | (uintptr_t)noise | (uintptr_t)coef | (uintptr_t)step_index |
+                                      (uintptr_t)z0 | (uintptr_t)x | (uintptr_t)mask) & 3))
+        return C2D_E_ALIGN;
+    const size_t tot = (size_t)n * h * w;
+    hipLaunchKernelGGL(inpaint_prepare_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const f16*)moments, ld, eps, noise, mask_u8, coef, step_index, pure_noise ? 1 : 0, n, h, w,
+                       scaling, z0, x, mask);
     return check_launch();
 }
 

@@ -579,6 +579,39 @@ def composite_u8(decoded: torch.Tensor, original: torch.Tensor, mask_u8: torch.T
     return out
 
 
+def inpaint_prepare(moments: torch.Tensor, noise: torch.Tensor, mask_u8: torch.Tensor, scaling: float,
+                    eps: torch.Tensor | None = None, coef: torch.Tensor | None = None,
+                    step_index: torch.Tensor | None = None, pure_noise: bool = False, z0: torch.Tensor | None = None,
+                    x: torch.Tensor | None = None, mask: torch.Tensor | None = None):
+    """The entry into the inpainting loop in one launch (c2d::inpaint_prepare) -> (z0, x, mask): moments fp16
+    [N * h * w, >= 8] and noise fp32 [N, 4, h, w] as vae_posterior_noise takes them, mask_u8 uint8 [N, 8h, 8w].
+    z0 = (mean + std * eps) * scaling (eps None: the mode); x = noise when pure_noise (the loop starts at step 0),
+    else add_noise(z0, noise) at the alpha coef[2 * step_index] read on the device; mask fp32 [N, h, w] as
+    mask_to_latent gives it.  x must not be noise or z0."""
+    _require(moments, "moments")
+    assert moments.dim() == 2 and moments.dtype == F16 and moments.stride(1) == 1 and moments.shape[1] >= 8
+    assert noise.dtype == torch.float32 and noise.is_contiguous() and noise.dim() == 4 and noise.shape[1] == 4
+    n, _, hgt, wid = noise.shape
+    assert moments.shape[0] == n * hgt * wid
+    assert mask_u8.dtype == torch.uint8 and mask_u8.is_contiguous() and mask_u8.is_cuda
+    assert tuple(mask_u8.shape) == (n, 8 * hgt, 8 * wid), f"mask {tuple(mask_u8.shape)} for latents {tuple(noise.shape)}"
+    if z0 is None:
+        z0 = torch.empty_like(noise)
+    if x is None:
+        x = torch.empty_like(noise)
+    if mask is None:
+        mask = torch.empty((n, hgt, wid), device=noise.device, dtype=torch.float32)
+    for t in (eps, noise, z0, x):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.shape == noise.shape and t.is_cuda)
+    assert x is not noise and x is not z0
+    assert mask.dtype == torch.float32 and mask.is_contiguous() and tuple(mask.shape) == (n, hgt, wid)
+    if not pure_noise:
+        assert coef is not None and step_index is not None and coef.dtype == torch.float32
+        assert step_index.dtype == torch.int32
+    C2D.inpaint_prepare(moments, eps, noise, mask_u8, coef, step_index, bool(pure_noise), float(scaling), z0, x, mask)
+    return z0, x, mask
+
+
 def upsample_nearest2x(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """NHWC fp16 nearest x2 (diffusers Upsample2D interpolate step)."""
     n, h, w, c = x.shape

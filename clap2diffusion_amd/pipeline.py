@@ -97,6 +97,49 @@ def initial_latents_and_eps(seeds: list[int], h: int, w: int, device=None) -> tu
     return torch.stack(lat).to(device), torch.stack(eps).to(device)
 
 
+def _mask_planes(m) -> list[np.ndarray]:
+    """One mask argument -> its uint8 [H, W] planes (prepare_mask_array's accepted forms, lists aside)."""
+    if isinstance(m, torch.Tensor):
+        m = m.detach().cpu().numpy()
+    if isinstance(m, (str, os.PathLike)):
+        from PIL import Image
+        m = Image.open(m)
+    if not isinstance(m, np.ndarray):
+        if not hasattr(m, "convert"):
+            raise ValueError(f"a mask must be a PIL image, a path or a uint8 / bool array, got {type(m).__name__}")
+        m = np.asarray(m.convert("L"), dtype=np.uint8)
+    if m.dtype == np.bool_:
+        m = m.astype(np.uint8) * 255
+    if m.dtype != np.uint8:
+        raise ValueError(f"a mask array must be uint8 (>= 128 = repaint) or bool, got {m.dtype}")
+    if m.ndim not in (2, 3):
+        raise ValueError(f"a mask array must be [H, W] or [B, H, W], got shape {tuple(m.shape)}")
+    return [m] if m.ndim == 2 else list(m)
+
+
+def prepare_mask_array(masks, height: int, width: int, n: int | None = None) -> np.ndarray:
+    """Inpainting mask(s) -> uint8 [B, height, width] on the host, >= 128 = repaint, < 128 = keep.  Accepted: a
+    PIL image (converted to "L"), a path, a numpy or torch uint8 array [H, W] / [B, H, W], a bool array
+    (True -> 255), or a list of those; resized with NEAREST where the size differs, so the bytes stay the
+    mask's own.  One mask given for n requests is repeated; any other count, dtype or rank is a ValueError."""
+    planes = []
+    for m in (masks if isinstance(masks, (list, tuple)) else [masks]):
+        planes.extend(_mask_planes(m))
+    if not planes:
+        raise ValueError("no mask given")
+    for k, m in enumerate(planes):
+        if m.shape != (height, width):
+            from PIL import Image
+            planes[k] = np.asarray(Image.fromarray(np.ascontiguousarray(m)).resize((width, height), Image.NEAREST),
+                                   dtype=np.uint8)
+    out = np.ascontiguousarray(np.stack(planes), dtype=np.uint8)
+    if n is not None and out.shape[0] != n:
+        if out.shape[0] != 1:
+            raise ValueError(f"{out.shape[0]} masks for {n} requests")
+        out = np.ascontiguousarray(np.repeat(out, n, axis=0))
+    return out
+
+
 _WAVE_PCM, _WAVE_FLOAT, _WAVE_EXTENSIBLE = 1, 3, 0xFFFE
 
 
@@ -356,6 +399,21 @@ class AudioToImageInference:
         """Image(s) (prepare_images forms) -> scaled latents fp32 [B, 4, H/8, W/8]; eps None = the posterior mode."""
         return self.vae_encoder.encode(self.prepare_images(images), eps)
 
+    def prepare_masks(self, masks, n: int | None = None) -> torch.Tensor:
+        """Inpainting mask(s) (prepare_mask_array forms) -> uint8 [B, H, W] on the device at the pipeline's size,
+        >= 128 = repaint.  A uint8 device tensor of that size and count is used as it is."""
+        if isinstance(masks, torch.Tensor) and masks.is_cuda and masks.dtype == torch.uint8 and masks.dim() == 3 \
+                and tuple(masks.shape[1:]) == (self.height, self.width) and n in (None, masks.shape[0]):
+            return masks.to(self.device).contiguous()
+        return torch.from_numpy(prepare_mask_array(masks, self.height, self.width, n)).to(self.device)
+
+    @staticmethod
+    def _check_masks(masks: torch.Tensor, imgs: torch.Tensor | None) -> None:
+        if imgs is None:
+            raise ValueError("a mask needs an init image: inpainting repaints a region of it (init_image= / init_images=)")
+        if tuple(masks.shape) != tuple(imgs.shape[:3]):
+            raise ValueError(f"masks {tuple(masks.shape)} do not match init images {tuple(imgs.shape)}")
+
     def _request_latents(self, n: int, seed, with_eps: bool = False):
         """Initial latents of n requests as the reference's generate() seeds them
         (scripts/inference.py:113-116: torch.manual_seed(seed) / np.random.seed(seed) when a seed
@@ -379,10 +437,17 @@ class AudioToImageInference:
 
     @torch.no_grad()
     def generate(self, audio_path, text_prompt="", num_inference_steps=50, guidance_scale=7.5, seed=None,
-                 use_hierarchical=True, init_image=None, strength=0.8, sample_posterior=True):
+                 use_hierarchical=True, init_image=None, strength=0.8, sample_posterior=True, mask=None,
+                 composite=True):
         """init_image (a PIL image, a path or a uint8 tensor [1, H, W, 3]): audio-guided image-to-image, the
         schedule entered at DDIMScheduler.img2img_start(steps, strength) from the encoded image plus scheduled
-        noise; sample_posterior=False takes the VAE posterior's mode instead of a sample."""
+        noise; sample_posterior=False takes the VAE posterior's mode instead of a sample.
+        mask (prepare_mask_array forms; >= 128 = repaint, < 128 = keep) with init_image: audio-guided inpainting
+        (diffusers StableDiffusionInpaintPipeline with a 4-channel UNet): after every step the kept latents are
+        set back to the image's, re-noised to that step; strength 1 starts from pure noise.  composite: the kept
+        pixels of the result are the init image's own bytes, else the plain decode."""
+        if mask is not None and init_image is None:
+            raise ValueError("mask= needs init_image=: inpainting repaints a region of that image")
         audio = self.load_audio(audio_path)
         if init_image is None:
             img = self.generate_batch(self.mel_features([audio]), [text_prompt], num_inference_steps, guidance_scale,
@@ -391,7 +456,8 @@ class AudioToImageInference:
         lat, eps = self._request_latents(1, seed, with_eps=True)
         img = self.generate_batch(self.mel_features([audio]), [text_prompt], num_inference_steps, guidance_scale,
                                   use_hierarchical=use_hierarchical, latents=lat, init_images=init_image,
-                                  strength=strength, posterior_eps=eps if sample_posterior else None)
+                                  strength=strength, posterior_eps=eps if sample_posterior else None,
+                                  masks=mask, composite=composite)
         return self.to_pil(img)[0]
 
     def batch_generate(self, audio_paths, text_prompts=None, **kwargs):
@@ -405,6 +471,9 @@ class AudioToImageInference:
         seed = kwargs.get("seed", None)
         mel = self.mel_features([self.load_audio(p) for p in audio_paths])
         init_images = kwargs.get("init_images", None)
+        masks = kwargs.get("masks", None)   # masks= (one per item, or one for all), composite= as generate()
+        if masks is not None and init_images is None:
+            raise ValueError("masks= needs init_images=: inpainting repaints a region of those images")
         if init_images is None:
             img = self.generate_batch(mel, list(text_prompts), steps, g,
                                       use_hierarchical=kwargs.get("use_hierarchical", True),
@@ -415,7 +484,8 @@ class AudioToImageInference:
         img = self.generate_batch(mel, list(text_prompts), steps, g,
                                   use_hierarchical=kwargs.get("use_hierarchical", True), latents=lat,
                                   init_images=init_images, strength=kwargs.get("strength", 0.8),
-                                  posterior_eps=eps if kwargs.get("sample_posterior", True) else None)
+                                  posterior_eps=eps if kwargs.get("sample_posterior", True) else None,
+                                  masks=masks, composite=kwargs.get("composite", True))
         return self.to_pil(img)
 
     # ------------------------------------------------------------ batched core
@@ -461,14 +531,21 @@ class AudioToImageInference:
                        guidance_scale: float = 7.5, seeds: list[int] | None = None, use_hierarchical: bool = True,
                        ids: tuple | None = None, latents: torch.Tensor | None = None, init_images=None,
                        strength: float = 0.8, posterior_eps: torch.Tensor | None = None,
-                       sample_posterior: bool = True) -> torch.Tensor:
+                       sample_posterior: bool = True, masks=None, composite: bool = True) -> torch.Tensor:
         """mel [B, 1001, 64] on device -> uint8 images NHWC [B, H, W, 3] on device.  The
         image size follows the latents ([B, 4, H/8, W/8]; default: the pipeline's size).
         init_images (prepare_images forms; the pipeline's size): image-to-image.  The images are encoded, the
         posterior sampled with posterior_eps [B, 4, H/8, W/8] (None: drawn after each sample's initial noise from
         its seed's generator when sample_posterior, else the mode), noised with `latents` to
         timesteps[t_start] (c2d_vae_posterior_noise, alpha read through the device step counter) and the last
-        steps - t_start steps run, t_start = DDIMScheduler.img2img_start(steps, strength)."""
+        steps - t_start steps run, t_start = DDIMScheduler.img2img_start(steps, strength).
+        masks (prepare_mask_array forms; the pipeline's size) with init_images: inpainting.  One launch
+        (c2d_inpaint_prepare) writes the sampler's z0 (the scaled posterior sample or mode), its first latents (z0
+        noised to timesteps[t_start], or `latents` themselves when t_start is 0) and its latent mask; the masked
+        step (c2d_cfg_ddim_step_masked) runs steps - t_start times; with composite the kept pixels of the decode are
+        set back to the init images' bytes (c2d_composite_u8)."""
+        if masks is not None and init_images is None:
+            raise ValueError("masks= needs init_images=: inpainting repaints a region of those images")
         b = mel.shape[0]
         if ids is None:
             ids = (self.tokenizer([""] * b, self.device), self.tokenizer(prompts or [""] * b, self.device))
@@ -477,6 +554,9 @@ class AudioToImageInference:
         if init_images is not None:
             t_start = DDIMScheduler.img2img_start(num_inference_steps, strength)
             imgs = self.prepare_images(init_images, b)
+            if masks is not None:
+                masks = self.prepare_masks(masks, b)
+                self._check_masks(masks, imgs)
             if latents is None and posterior_eps is None and sample_posterior:
                 latents, posterior_eps = initial_latents_and_eps(seeds if seeds is not None else list(range(b)),
                                                                  self.height // 8, self.width // 8, self.device)
@@ -494,6 +574,14 @@ class AudioToImageInference:
         noise = latents.to(self.device, torch.float32).contiguous()
         eps = posterior_eps.to(self.device, torch.float32).contiguous() if posterior_eps is not None else None
         den.step_idx.fill_(t_start)   # the kernel reads the alpha of the first step that runs through the counter
+        if masks is not None:
+            den.masked_buffers()
+            # t_start 0 (strength 1): the loop starts from the noise itself (init_noise_sigma is 1 for DDIM)
+            ops.inpaint_prepare(self.vae_encoder(imgs), noise, masks, SCALING, eps=eps, coef=den.coef,
+                                step_index=den.step_idx, pure_noise=t_start == 0, z0=den.z0, x=den.x, mask=den.mask)
+            den.noise.copy_(noise)
+            img = self.vae(den.run(None, start=t_start, masked=True))
+            return ops.composite_u8(img, imgs, masks, out=img) if composite else img
         x0 = ops.vae_posterior_noise(self.vae_encoder(imgs), torch.empty_like(noise), SCALING, eps=eps, noise=noise,
                                      coef=den.coef, step_index=den.step_idx)
         return self.vae(den.run(x0, start=t_start))
@@ -503,7 +591,8 @@ class AudioToImageInference:
                                ids: tuple, latents: torch.Tensor, num_inference_steps: int = 50,
                                guidance_scale: float = 7.5, use_hierarchical: bool = True,
                                slot: int = 0, init_images: torch.Tensor | None = None, strength: float = 0.8,
-                               posterior_eps: torch.Tensor | None = None) -> torch.Tensor:
+                               posterior_eps: torch.Tensor | None = None, masks=None,
+                               composite: bool = True) -> torch.Tensor:
         """generate_batch from device-resident inputs (48 kHz clips concatenated + offsets /
         lengths, token ids, latents) as hipGraphs: one graph for the conditioning leg, the
         denoise-step graph replayed per DDIM step, one graph for the VAE decode (BatchGraph).
@@ -512,19 +601,30 @@ class AudioToImageInference:
         init_images (uint8 [B, H, W, 3] on the device, the latents' size x 8): image-to-image.  The conditioning
         graph then also runs the VAE encoder over a static image buffer, writes the noised latents into the
         sampler state (c2d_vae_posterior_noise; posterior_eps None = the mode) and sets the step counter to
-        t_start; steps - t_start replays of the same step graph follow."""
+        t_start; steps - t_start replays of the same step graph follow.
+        masks (uint8 [B, H, W] on the device, or any prepare_mask_array form) with init_images: inpainting.  The
+        conditioning graph then ends with c2d_inpaint_prepare over static image and mask buffers, the steps
+        replay the sampler's masked graph, and with composite the decode graph ends with c2d_composite_u8; a
+        call with another image or mask copies it into the static buffers and replays the same graphs."""
+        if masks is not None and init_images is None:
+            raise ValueError("masks= needs init_images=: inpainting repaints a region of those images")
         t_start = 0
         if init_images is not None:
             t_start = DDIMScheduler.img2img_start(num_inference_steps, strength)
             init_images = self.prepare_images(init_images, offsets.numel())
+        if masks is not None:
+            masks = self.prepare_masks(masks, offsets.numel())
+            self._check_masks(masks, init_images)
+        composite = bool(composite) and masks is not None
         key = (offsets.numel(), wave.numel(), num_inference_steps, float(guidance_scale), tuple(latents.shape),
-               bool(use_hierarchical), slot, t_start, init_images is not None, posterior_eps is not None)
+               bool(use_hierarchical), slot, masks is not None, composite, t_start, init_images is not None,
+               posterior_eps is not None)
         bg = self._batch_graphs.get(key)
         if bg is None:
             bg = BatchGraph(self, wave, offsets, lengths, ids, latents, num_inference_steps, guidance_scale,
-                            use_hierarchical, slot, init_images, t_start, posterior_eps)
+                            use_hierarchical, slot, init_images, t_start, posterior_eps, masks, composite)
             self._batch_graphs[key] = bg
-        return bg.run(wave, offsets, lengths, ids, latents, init_images, posterior_eps)
+        return bg.run(wave, offsets, lengths, ids, latents, init_images, posterior_eps, masks)
 
     @staticmethod
     def to_pil(images: torch.Tensor):
@@ -543,13 +643,21 @@ class BatchGraph:
     latents; all workspaces come from the graphs' private pools (allocated at capture).
     With init images (img2img) g_cond also holds the VAE encoder over a static image buffer and
     c2d_vae_posterior_noise writing the sampler state, and sets the step counter to t_start; the step graph
-    is the text-to-image one, replayed steps - t_start times."""
+    is the text-to-image one, replayed steps - t_start times.
+    With masks as well (inpainting) a static uint8 mask buffer joins the image's; g_cond ends with
+    c2d_inpaint_prepare writing the sampler's z0 / x / mask, the copy of the noise into its noise buffer and the
+    counter set to t_start; the steps replay the sampler's masked graph; with composite g_vae ends with
+    c2d_composite_u8 into the static image."""
 
     def __init__(self, pipe: AudioToImageInference, wave, offsets, lengths, ids, latents, steps: int,
                  guidance: float, use_hierarchical: bool, slot: int = 0, init_images=None, t_start: int = 0,
-                 posterior_eps=None):
+                 posterior_eps=None, masks=None, composite: bool = True):
         self.pipe, self.steps, self.use_hier = pipe, steps, use_hierarchical
         self.t_start = t_start
+        if masks is not None and init_images is None:
+            raise ValueError("masks need init images")
+        self.masks = masks.clone() if masks is not None else None
+        self.composite = bool(composite) and masks is not None
         self.images = init_images.clone() if init_images is not None else None
         self.eps = posterior_eps.float().clone() if posterior_eps is not None else None
         self.enc = pipe.vae_encoder if init_images is not None else None
@@ -567,18 +675,28 @@ class BatchGraph:
         self.den.prepare_context()
         if self.den.use_graph and self.den.graph is None:
             self.den.capture()
+        if self.masks is not None:
+            self.den.masked_buffers()
+            if self.den.use_graph and self.den.graph_masked is None:
+                self.den.capture_masked()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             self._cond()
-            pipe.vae(self.den.x)
+            self._decode()
         torch.cuda.current_stream().wait_stream(side)
         self.g_cond = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_cond):
             self._cond()
         self.g_vae = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_vae):
-            self.img = pipe.vae(self.den.x)
+            self.img = self._decode()
+
+    def _decode(self) -> torch.Tensor:
+        img = self.pipe.vae(self.den.x)
+        if self.composite:
+            ops.composite_u8(img, self.images, self.masks, out=img)
+        return img
 
     def _cond(self) -> None:
         pipe, den = self.pipe, self.den
@@ -593,14 +711,23 @@ class BatchGraph:
             den.step_idx.zero_()
             return
         den.step_idx.fill_(self.t_start)
+        if self.masks is not None:
+            ops.inpaint_prepare(self.enc(self.images), self.lat, self.masks, SCALING, eps=self.eps, coef=den.coef,
+                                step_index=den.step_idx, pure_noise=self.t_start == 0, z0=den.z0, x=den.x,
+                                mask=den.mask)
+            den.noise.copy_(self.lat)
+            return
         ops.vae_posterior_noise(self.enc(self.images), den.x, SCALING, eps=self.eps, noise=self.lat, coef=den.coef,
                                 step_index=den.step_idx)
 
-    def run(self, wave, offsets, lengths, ids, latents, init_images=None, posterior_eps=None) -> torch.Tensor:
+    def run(self, wave, offsets, lengths, ids, latents, init_images=None, posterior_eps=None,
+            masks=None) -> torch.Tensor:
         pairs = [(self.wave, wave), (self.offs, offsets), (self.lens, lengths), (self.ids_u, ids[0]),
                  (self.ids_c, ids[1]), (self.lat, latents)]
         if self.images is not None:
             pairs.append((self.images, init_images))
+        if self.masks is not None:
+            pairs.append((self.masks, masks))
         if self.eps is not None:
             pairs.append((self.eps, posterior_eps))
         for dst, src in pairs:
@@ -608,13 +735,16 @@ class BatchGraph:
                 dst.copy_(src)
         self.g_cond.replay()
         for _ in range(self.steps - self.t_start):
-            self.den.graph.replay() if self.den.use_graph else self.den._body()
+            if self.masks is not None:
+                self.den.step_masked()
+            else:
+                self.den.graph.replay() if self.den.use_graph else self.den._body()
         self.g_vae.replay()
         self.pipe.last_denoiser = self.den
         return self.img
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="CLAP2Diffusion Inference (MI355X HIP path)")
     ap.add_argument("--audio", type=str, required=True, help="Path to audio file (or synthetic:<seed>)")
     ap.add_argument("--text", type=str, default="", help="Text prompt")
@@ -628,11 +758,21 @@ def main():
     ap.add_argument("--clap_model", type=str, default=None, help="ClapModel weights file or folder")
     ap.add_argument("--init_image", type=str, default=None, help="Start from this image (audio-guided img2img)")
     ap.add_argument("--strength", type=float, default=0.8, help="img2img strength in (0, 1]: 1 = ignore the image")
-    a = ap.parse_args()
+    ap.add_argument("--mask", type=str, default=None,
+                    help="Inpaint --init_image: a grey-scale image, >= 128 = repaint, < 128 = keep")
+    ap.add_argument("--no_composite", action="store_true",
+                    help="With --mask: return the plain decode instead of pasting the kept pixels back")
+    return ap
+
+
+def main():
+    a = build_parser().parse_args()
+    if a.mask is not None and a.init_image is None:
+        raise SystemExit("--mask needs --init_image")
     pipe = AudioToImageInference(checkpoint_dir=a.checkpoint_dir, sd_model_path=a.sd_model, clap_model_path=a.clap_model)
     img = pipe.generate(audio_path=a.audio, text_prompt=a.text, num_inference_steps=a.steps,
                         guidance_scale=a.cfg_scale, seed=a.seed, use_hierarchical=not a.no_hierarchical,
-                        init_image=a.init_image, strength=a.strength)
+                        init_image=a.init_image, strength=a.strength, mask=a.mask, composite=not a.no_composite)
     img.save(a.output)
     print(f"Image saved to {a.output}")
 

@@ -317,6 +317,18 @@ def composite_u8(decoded: Tensor, original: Tensor, mask_u8: Tensor, out: Tensor
           "c2d_composite_u8")
 
 
+@custom_op("c2d::inpaint_prepare", mutates_args=("z0", "x", "mask"), device_types=_CU)
+def inpaint_prepare(moments: Tensor, eps: Optional[Tensor], noise: Tensor, mask_u8: Tensor, coef: Optional[Tensor],
+                    step_index: Optional[Tensor], pure_noise: bool, scaling: float, z0: Tensor, x: Tensor,
+                    mask: Tensor) -> None:
+    """c2d_inpaint_prepare: moments fp16 [n * h * w][ld], mask_u8 [n][8h][8w] -> z0, x fp32 [n][4][h][w] and mask
+    fp32 [n][h][w] (the posterior sample or mode * scaling, the loop's first latents, the latent mask)."""
+    n, h, w = mask.shape
+    check(lib().c2d_inpaint_prepare(ptr(moments), moments.stride(0), ptr(eps), ptr(noise), ptr(mask_u8), ptr(coef),
+                                    ptr(step_index), int(pure_noise), n, h, w, scaling, ptr(z0), ptr(x), ptr(mask),
+                                    stream_ptr()), "c2d_inpaint_prepare")
+
+
 @custom_op("c2d::upsample_nearest2x", mutates_args=("out",), device_types=_CU)
 def upsample_nearest2x(x: Tensor, out: Tensor) -> None:
     n, h, w, c = x.shape
@@ -332,7 +344,7 @@ def add(a: Tensor, b: Tensor, out: Tensor) -> None:
 for _op in (pack_weights, groupnorm_stats, groupnorm_apply, groupnorm, groupnorm_pad, groupnorm_moments, layernorm_stats, layernorm, attention_fwd,
             attention_small, window_attention, htsat_mel_patches, patch_merge_gather, row_mean, softmax_rows,
             l2_normalize, clap_log_mel, timestep_embedding, cfg_ddim_step, latent_to_nhwc, upsample_nearest2x, add,
-            image_to_nhwc, vae_posterior_noise, cfg_ddim_step_masked, mask_to_latent, composite_u8):
+            image_to_nhwc, vae_posterior_noise, cfg_ddim_step_masked, mask_to_latent, composite_u8, inpaint_prepare):
     _op.register_fake(lambda *args, **kwargs: None)
 
 OPS = ("conv2d_igemm", "pack_weights", "groupnorm_stats", "groupnorm_apply", "groupnorm", "groupnorm_pad", "groupnorm_moments",
@@ -340,4 +352,4 @@ OPS = ("conv2d_igemm", "pack_weights", "groupnorm_stats", "groupnorm_apply", "gr
        "layernorm", "attention_fwd", "attention_small", "window_attention", "htsat_mel_patches", "patch_merge_gather",
        "row_mean", "softmax_rows", "l2_normalize", "clap_log_mel", "timestep_embedding", "cfg_ddim_step",
        "latent_to_nhwc", "upsample_nearest2x", "add", "image_to_nhwc", "vae_posterior_noise",
-       "cfg_ddim_step_masked", "mask_to_latent", "composite_u8")
+       "cfg_ddim_step_masked", "mask_to_latent", "composite_u8", "inpaint_prepare")

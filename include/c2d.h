@@ -516,6 +516,29 @@ int c2d_mask_to_latent(const uint8_t* mask_u8, int n, int h, int w, float* out, 
 int c2d_composite_u8(const uint8_t* decoded, const uint8_t* original, const uint8_t* mask_u8, size_t npix,
                      uint8_t* out, void* stream);
 
+/*
+ * The entry into the inpainting loop in one launch (added to the r7 ABI: no struct changed): the posterior
+ * sample of the init image, the loop's first latents and the latent mask, i.e. c2d_vae_posterior_noise twice
+ * (without and with noise) and c2d_mask_to_latent.  moments fp16 [n * h * w][ld] (ld >= 8) as
+ * c2d_vae_posterior_noise reads it; eps (NULL = the mode) and noise fp32 NCHW [n][4][h * w]; mask_u8
+ * [n][8h][8w]; outputs z0 and x fp32 NCHW [n][4][h * w], mask fp32 [n][h][w].  fp32 throughout:
+ *   z0   = (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps) * scaling
+ *   x    = noise                                        pure_noise != 0 (the loop starts at step 0: diffusers'
+ *                                                       is_strength_max; coef / step_index unused, may be NULL)
+ *          sqrt(a) z0 + sqrt(1 - a) noise, a = coef[2 * (*step_index)]     otherwise
+ *   mask = mask_u8[8y][8x] >= 128 ? 1 : 0
+ * coef is c2d_cfg_ddim_step's (alpha_t, alpha_prev) table; the counter is read on the device (graph-capturable)
+ * and never advanced.  x must not alias noise or z0 (each is read or written per channel while the others are
+ * live), and no output may overlap an input.  Replaces, for a 4-channel UNet, prepare_latents / prepare_mask_latents
+ * of diffusers 0.23.1 StableDiffusionInpaintPipeline.
+ * C2D_E_ARG: null moments, noise, mask_u8, z0, x or mask, or null coef / step_index when !pure_noise;
+ * C2D_E_SHAPE: n, h or w <= 0, or ld < 8; C2D_E_ALIGN: moments not 2-byte or an fp32 / int pointer not 4-byte
+ * aligned; all before any launch.
+ */
+int c2d_inpaint_prepare(const void* moments, int ld, const float* eps, const float* noise, const uint8_t* mask_u8,
+                        const float* coef, const int* step_index, int pure_noise, int n, int h, int w,
+                        float scaling, float* z0, float* x, float* mask, void* stream);
+
 /* Nearest-neighbour x2 upsample of NHWC fp16 [n, h, w, c] -> [n, 2h, 2w, c], c % 8 == 0.
  * Replaces F.interpolate(scale_factor=2.0, mode="nearest") in diffusers Upsample2D
  * (the UNet up path and the VAE decoder). */
