@@ -23,23 +23,24 @@ import argparse
 import os
 import warnings
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import weights as W
+from .audio_io import SR, _read_wav, read_audio, synthetic_thunder  # noqa: F401  (_read_wav: imported from here)
 from .features import ClapLogMel
 from .htsat import HTSATEncoder
+from .image_io import prepare_image_array, prepare_mask_array
 from .processor import AudioProcessorManager
 from .projectors import AudioAdapter, HierarchicalAudioV4, ImprovedHierarchicalAudioEncoder, normalize_tokens
 from .sampler import GraphDenoiser
 from .scheduler import DDIMScheduler
 from .text_encoder import TextEncoder, make_tokenizer
 from .unet import UNet2DConditionModel
-from .vae import SCALING, VAEDecoder, VAEEncoder
+from .vae import VAEDecoder, VAEEncoder
 from . import ops
-
-SR = 48000
 
 # Supported image sizes: the UNet halves the 8x-downsampled latent three times and concatenates each level with
 # its skip on the way up, so the latent height and width must be multiples of 8 (pixels: of 64); the smallest,
@@ -66,180 +67,34 @@ def check_latent_size(h: int, w: int) -> None:
     check_image_size(8 * int(h), 8 * int(w))
 
 
-def synthetic_thunder(seed: int = 0, seconds: float = 10.0, sr: int = SR) -> np.ndarray:
-    """SURVEY.md §8(d) stand-in for the LFS-stub assets/Thunder.wav: low-passed white
-    noise with three exponentially decaying bursts, peak-normalised."""
-    from scipy.signal import lfilter
-    rs = np.random.RandomState(seed)
-    n = int(seconds * sr)
-    y = lfilter([0.005], [1.0, -0.995], rs.randn(n))  # 1-pole IIR low-pass, a = 0.995
-    t = np.arange(n) / sr
-    env = 0.05 + sum(np.where(t >= t0, np.exp(-(t - t0) / 0.6), 0.0) for t0 in (1.0, 4.5, 7.0))
-    y = y * env
-    return (y / (np.abs(y).max() + 1e-8)).astype(np.float32)
+def _seeded_noise(seeds: list[int], h: int, w: int, device, draws: int) -> list[torch.Tensor]:
+    """`draws` tensors [B, 4, h, w], drawn one after the other from each sample's own CPU generator
+    (torch.Generator().manual_seed(seed)): identical on any number of GPUs."""
+    gens = [torch.Generator().manual_seed(int(s)) for s in seeds]
+    per_sample = [[torch.randn(4, h, w, generator=g) for _ in range(draws)] for g in gens]
+    return [torch.stack(t).to(device) for t in zip(*per_sample)]
 
 
 def initial_latents(seeds: list[int], h: int, w: int, device=None) -> torch.Tensor:
-    """Per-sample CPU generator (torch.Generator().manual_seed(seed) -> randn [4, h, w]):
-    identical latents on any number of GPUs."""
-    lat = [torch.randn(4, h, w, generator=torch.Generator().manual_seed(int(s))) for s in seeds]
-    return torch.stack(lat).to(device)
+    """The initial noise of each sample: the first draw of its generator."""
+    return _seeded_noise(seeds, h, w, device, 1)[0]
 
 
 def initial_latents_and_eps(seeds: list[int], h: int, w: int, device=None) -> tuple[torch.Tensor, torch.Tensor]:
     """img2img noise: each sample's generator draws the initial noise (the same tensor initial_latents gives)
     and, right after it, the posterior noise of the VAE encoder's sample."""
-    lat, eps = [], []
-    for s in seeds:
-        g = torch.Generator().manual_seed(int(s))
-        lat.append(torch.randn(4, h, w, generator=g))
-        eps.append(torch.randn(4, h, w, generator=g))
-    return torch.stack(lat).to(device), torch.stack(eps).to(device)
+    lat, eps = _seeded_noise(seeds, h, w, device, 2)
+    return lat, eps
 
 
-def _mask_planes(m) -> list[np.ndarray]:
-    """One mask argument -> its uint8 [H, W] planes (prepare_mask_array's accepted forms, lists aside)."""
-    if isinstance(m, torch.Tensor):
-        m = m.detach().cpu().numpy()
-    if isinstance(m, (str, os.PathLike)):
-        from PIL import Image
-        m = Image.open(m)
-    if not isinstance(m, np.ndarray):
-        if not hasattr(m, "convert"):
-            raise ValueError(f"a mask must be a PIL image, a path or a uint8 / bool array, got {type(m).__name__}")
-        m = np.asarray(m.convert("L"), dtype=np.uint8)
-    if m.dtype == np.bool_:
-        m = m.astype(np.uint8) * 255
-    if m.dtype != np.uint8:
-        raise ValueError(f"a mask array must be uint8 (>= 128 = repaint) or bool, got {m.dtype}")
-    if m.ndim not in (2, 3):
-        raise ValueError(f"a mask array must be [H, W] or [B, H, W], got shape {tuple(m.shape)}")
-    return [m] if m.ndim == 2 else list(m)
-
-
-def prepare_mask_array(masks, height: int, width: int, n: int | None = None) -> np.ndarray:
-    """Inpainting mask(s) -> uint8 [B, height, width] on the host, >= 128 = repaint, < 128 = keep.  Accepted: a
-    PIL image (converted to "L"), a path, a numpy or torch uint8 array [H, W] / [B, H, W], a bool array
-    (True -> 255), or a list of those; resized with NEAREST where the size differs, so the bytes stay the
-    mask's own.  One mask given for n requests is repeated; any other count, dtype or rank is a ValueError."""
-    planes = []
-    for m in (masks if isinstance(masks, (list, tuple)) else [masks]):
-        planes.extend(_mask_planes(m))
-    if not planes:
-        raise ValueError("no mask given")
-    for k, m in enumerate(planes):
-        if m.shape != (height, width):
-            from PIL import Image
-            planes[k] = np.asarray(Image.fromarray(np.ascontiguousarray(m)).resize((width, height), Image.NEAREST),
-                                   dtype=np.uint8)
-    out = np.ascontiguousarray(np.stack(planes), dtype=np.uint8)
-    if n is not None and out.shape[0] != n:
-        if out.shape[0] != 1:
-            raise ValueError(f"{out.shape[0]} masks for {n} requests")
-        out = np.ascontiguousarray(np.repeat(out, n, axis=0))
-    return out
-
-
-_WAVE_PCM, _WAVE_FLOAT, _WAVE_EXTENSIBLE = 1, 3, 0xFFFE
-
-
-def _read_wav(path: str, max_seconds: float | None = None) -> tuple[np.ndarray, int]:
-    """RIFF/WAVE reader -> (mono float32 in [-1, 1], native rate): PCM 8 (unsigned) / 16 / 24 / 32-bit,
-    IEEE float 32 / 64-bit, WAVE_FORMAT_EXTENSIBLE of either; channels averaged (librosa mono=True).
-    max_seconds: keep the first max_seconds of the file at its native rate (librosa's duration=,
-    applied before resampling as librosa.load does).  read_audio adds AIFF / AIFC and Sun AU; other
-    containers (mp3, flac, ...) need a decoder this image does not have: convert them first."""
-    data = Path(path).read_bytes()
-    if data[:4] != b"RIFF" or data[8:12] != b"WAVE":
-        raise ValueError(f"{path}: not a RIFF/WAVE file (only WAV is decoded without librosa)")
-    fmt = None
-    pos = 12
-    body = None
-    while pos + 8 <= len(data):
-        cid, size = data[pos:pos + 4], int.from_bytes(data[pos + 4:pos + 8], "little")
-        chunk = data[pos + 8:pos + 8 + size]
-        if cid == b"fmt ":
-            tag, ch, sr = int.from_bytes(chunk[0:2], "little"), int.from_bytes(chunk[2:4], "little"), \
-                int.from_bytes(chunk[4:8], "little")
-            bits = int.from_bytes(chunk[14:16], "little")
-            if tag == _WAVE_EXTENSIBLE and len(chunk) >= 26:
-                tag = int.from_bytes(chunk[24:26], "little")   # first two bytes of the SubFormat GUID
-            fmt = (tag, ch, sr, bits)
-        elif cid == b"data":
-            body = chunk
-        pos += 8 + size + (size & 1)
-    if fmt is None or body is None:
-        raise ValueError(f"{path}: WAV without fmt / data chunk")
-    tag, ch, sr, bits = fmt
-    bps = bits // 8
-    frames = len(body) // (bps * ch)
-    if max_seconds is not None:
-        frames = min(frames, int(max_seconds * sr))
-    body = body[: frames * bps * ch]
-    if tag == _WAVE_FLOAT and bits in (32, 64):
-        x = np.frombuffer(body, dtype=np.float32 if bits == 32 else np.float64).astype(np.float32)
-    elif tag == _WAVE_PCM and bits == 8:
-        x = (np.frombuffer(body, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
-    elif tag == _WAVE_PCM and bits in (16, 32):
-        x = np.frombuffer(body, dtype=np.int16 if bits == 16 else np.int32).astype(np.float32) / float(2 ** (bits - 1))
-    elif tag == _WAVE_PCM and bits == 24:
-        b = np.frombuffer(body, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
-        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
-        v = np.where(v >= 1 << 23, v - (1 << 24), v)
-        x = v.astype(np.float32) / float(1 << 23)
-    else:
-        raise ValueError(f"{path}: unsupported WAV encoding (format tag {tag}, {bits} bits)")
-    return x.reshape(-1, ch).mean(axis=1), sr
-
-
-def _pcm_to_float(raw: bytes, width: int, big: bool) -> np.ndarray:
-    """Signed linear PCM of `width` bytes per sample -> float32 in [-1, 1)."""
-    if width == 1:
-        return np.frombuffer(raw, dtype=np.int8).astype(np.float32) / 128.0
-    if width == 3:
-        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
-        v = (b[:, 0] << 16 | b[:, 1] << 8 | b[:, 2]) if big else (b[:, 0] | b[:, 1] << 8 | b[:, 2] << 16)
-        return (np.where(v >= 1 << 23, v - (1 << 24), v)).astype(np.float32) / float(1 << 23)
-    dt = {2: "i2", 4: "i4"}[width]
-    return np.frombuffer(raw, dtype=(">" if big else "<") + dt).astype(np.float32) / float(2 ** (8 * width - 1))
-
-
-def _read_stdlib(mod, path: str, max_seconds: float | None) -> tuple[np.ndarray, int]:
-    """AIFF / AIFC (aifc) and Sun AU (sunau) through the standard library's readers: linear PCM
-    8 / 16 / 24 / 32-bit (big-endian; AIFC 'sowt' comes back big-endian from aifc) and the
-    companded codecs those modules expand to native-endian 16-bit (u-law / a-law / G.722)."""
-    with mod.open(path, "rb") as f:
-        ch, width, sr, n = f.getnchannels(), f.getsampwidth(), f.getframerate(), f.getnframes()
-        if max_seconds is not None:
-            n = min(n, int(max_seconds * sr))
-        raw = f.readframes(n)
-        comp = f.getcomptype()
-    comp = comp.decode() if isinstance(comp, bytes) else str(comp)
-    big = comp.upper() in ("NONE", "SOWT") or comp == "not compressed"
-    if width not in (1, 2, 3, 4):
-        raise ValueError(f"{path}: unsupported sample width {width}")
-    x = _pcm_to_float(raw[: len(raw) // (width * ch) * width * ch], width, big)
-    return x.reshape(-1, ch).mean(axis=1), sr
-
-
-def read_audio(path: str, max_seconds: float | None = None) -> tuple[np.ndarray, int]:
-    """(mono float32, native rate) of a WAV, AIFF / AIFC or Sun AU file, chosen by its header (the
-    containers this image decodes without librosa; reference scripts/inference.py:78 reads any
-    format librosa does).  max_seconds: keep the first max_seconds at the native rate."""
-    head = Path(path).read_bytes()[:12]
-    if head[:4] == b"RIFF" and head[8:12] == b"WAVE":
-        return _read_wav(path, max_seconds)
-    import warnings
-    with warnings.catch_warnings():   # aifc / sunau are deprecated from Python 3.11 on
-        warnings.simplefilter("ignore", DeprecationWarning)
-        if head[:4] == b"FORM" and head[8:12] in (b"AIFF", b"AIFC"):
-            import aifc
-            return _read_stdlib(aifc, path, max_seconds)
-        if head[:4] == b".snd":
-            import sunau
-            return _read_stdlib(sunau, path, max_seconds)
-    raise ValueError(f"{path}: not a RIFF/WAVE, AIFF/AIFC or Sun AU file (other formats need a decoder this "
-                     "image does not have: convert them first)")
+class _Request(NamedTuple):
+    """What a call asked for beyond text-to-image, resolved (AudioToImageInference._resolve): the first step that
+    runs, the init images uint8 [B, H, W, 3] and masks uint8 [B, H, W] on the device (None: none given), and
+    whether the kept pixels are pasted back."""
+    t_start: int
+    images: torch.Tensor | None
+    masks: torch.Tensor | None
+    composite: bool
 
 
 class AudioToImageInference:
@@ -364,35 +219,13 @@ class AudioToImageInference:
         return self._vae_encoder
 
     def prepare_images(self, images, n: int | None = None) -> torch.Tensor:
-        """PIL image(s), path(s) or a uint8 tensor [B, H, W, 3] -> uint8 [B, H, W, 3] on the device at the
-        pipeline's size: converted to RGB and resized on the host (bicubic) where the size differs.  One
-        image given for n requests is repeated."""
-        if isinstance(images, torch.Tensor):
-            if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
-                raise ValueError(f"init images as a tensor must be uint8 [B, H, W, 3], got {images.dtype} "
-                                 f"{tuple(images.shape)}")
-            if tuple(images.shape[1:3]) == (self.height, self.width):
-                out = images.to(self.device).contiguous()
-            else:
-                images = list(images.cpu().numpy())
-        if not isinstance(images, torch.Tensor):
-            from PIL import Image
-            arr = []
-            for im in (list(images) if isinstance(images, (list, tuple)) else [images]):
-                if isinstance(im, (str, os.PathLike)):
-                    im = Image.open(im)
-                elif isinstance(im, np.ndarray):
-                    im = Image.fromarray(im)
-                im = im.convert("RGB")
-                if im.size != (self.width, self.height):
-                    im = im.resize((self.width, self.height), Image.BICUBIC)
-                arr.append(np.asarray(im, dtype=np.uint8))
-            out = torch.from_numpy(np.stack(arr)).to(self.device)
-        if n is not None and out.shape[0] != n:
-            if out.shape[0] != 1:
-                raise ValueError(f"{out.shape[0]} init images for {n} requests")
-            out = out.expand(n, -1, -1, -1).contiguous()
-        return out
+        """Init image(s) (prepare_image_array forms) -> uint8 [B, H, W, 3] on the device at the pipeline's size.  A
+        uint8 tensor of that size, one image or n of them, stays on its device (one is repeated for n requests)."""
+        if isinstance(images, torch.Tensor) and images.dtype == torch.uint8 and images.dim() == 4 \
+                and tuple(images.shape[1:]) == (self.height, self.width, 3) \
+                and (n is None or images.shape[0] in (1, n)):
+            return images.to(self.device).expand(n or -1, -1, -1, -1).contiguous()
+        return torch.from_numpy(prepare_image_array(images, self.height, self.width, n)).to(self.device)
 
     @torch.no_grad()
     def encode_image(self, images, eps: torch.Tensor | None = None) -> torch.Tensor:
@@ -407,21 +240,30 @@ class AudioToImageInference:
             return masks.to(self.device).contiguous()
         return torch.from_numpy(prepare_mask_array(masks, self.height, self.width, n)).to(self.device)
 
-    @staticmethod
-    def _check_masks(masks: torch.Tensor, imgs: torch.Tensor | None) -> None:
-        if imgs is None:
-            raise ValueError("a mask needs an init image: inpainting repaints a region of it (init_image= / init_images=)")
-        if tuple(masks.shape) != tuple(imgs.shape[:3]):
-            raise ValueError(f"masks {tuple(masks.shape)} do not match init images {tuple(imgs.shape)}")
+    def _resolve(self, b: int, steps: int, init_images, strength: float, masks, composite: bool) -> _Request:
+        """The init images and masks of b requests on the device (prepare_images / prepare_masks), the step the
+        schedule is entered at (DDIMScheduler.img2img_start; 0 for text-to-image) and whether to composite."""
+        if init_images is None:
+            if masks is not None:
+                raise ValueError("a mask needs an init image: inpainting repaints a region of it "
+                                 "(init_image= / init_images=)")
+            return _Request(0, None, None, False)
+        t_start = DDIMScheduler.img2img_start(steps, strength)
+        images = self.prepare_images(init_images, b)
+        if masks is not None:
+            masks = self.prepare_masks(masks, b)
+            if tuple(masks.shape) != tuple(images.shape[:3]):
+                raise ValueError(f"masks {tuple(masks.shape)} do not match init images {tuple(images.shape)}")
+        return _Request(t_start, images, masks, bool(composite) and masks is not None)
 
     def _request_latents(self, n: int, seed, with_eps: bool = False):
-        """Initial latents of n requests as the reference's generate() seeds them
+        """(latents, eps) of n requests as the reference's generate() seeds them
         (scripts/inference.py:113-116: torch.manual_seed(seed) / np.random.seed(seed) when a seed
         is given, the RNG left as it is otherwise): each request draws [1, 4, h/8, w/8] from the
         global CPU generator right after its (re-)seeding, so a given seed always yields
         initial_latents([seed]) and seed=None draws fresh noise every call.  with_eps (img2img with a sampled
         posterior): each request draws its posterior noise right after its initial noise, so a seed fixes
-        both; returns (latents, eps)."""
+        both; eps is None otherwise."""
         h, w = self.height // 8, self.width // 8
         lat, eps = [], []
         for _ in range(n):
@@ -431,11 +273,21 @@ class AudioToImageInference:
             lat.append(torch.randn(1, 4, h, w))
             if with_eps:
                 eps.append(torch.randn(1, 4, h, w))
-        if with_eps:
-            return torch.cat(lat).to(self.device), torch.cat(eps).to(self.device)
-        return torch.cat(lat).to(self.device)
+        return torch.cat(lat).to(self.device), torch.cat(eps).to(self.device) if with_eps else None
 
     @torch.no_grad()
+    def _generate(self, audio_paths, text_prompts, num_inference_steps=50, guidance_scale=7.5, seed=None,
+                  use_hierarchical=True, init_images=None, strength=0.8, sample_posterior=True, masks=None,
+                  composite=True, **_):
+        """generate() for a list of requests -> PIL images; keywords it does not know are ignored."""
+        mel = self.mel_features([self.load_audio(p) for p in audio_paths])
+        lat, eps = self._request_latents(len(audio_paths), seed, with_eps=init_images is not None)
+        img = self.generate_batch(mel, list(text_prompts), num_inference_steps, guidance_scale,
+                                  use_hierarchical=use_hierarchical, latents=lat, init_images=init_images,
+                                  strength=strength, posterior_eps=eps if sample_posterior else None, masks=masks,
+                                  composite=composite)
+        return self.to_pil(img)
+
     def generate(self, audio_path, text_prompt="", num_inference_steps=50, guidance_scale=7.5, seed=None,
                  use_hierarchical=True, init_image=None, strength=0.8, sample_posterior=True, mask=None,
                  composite=True):
@@ -446,47 +298,18 @@ class AudioToImageInference:
         (diffusers StableDiffusionInpaintPipeline with a 4-channel UNet): after every step the kept latents are
         set back to the image's, re-noised to that step; strength 1 starts from pure noise.  composite: the kept
         pixels of the result are the init image's own bytes, else the plain decode."""
-        if mask is not None and init_image is None:
-            raise ValueError("mask= needs init_image=: inpainting repaints a region of that image")
-        audio = self.load_audio(audio_path)
-        if init_image is None:
-            img = self.generate_batch(self.mel_features([audio]), [text_prompt], num_inference_steps, guidance_scale,
-                                      use_hierarchical=use_hierarchical, latents=self._request_latents(1, seed))
-            return self.to_pil(img)[0]
-        lat, eps = self._request_latents(1, seed, with_eps=True)
-        img = self.generate_batch(self.mel_features([audio]), [text_prompt], num_inference_steps, guidance_scale,
-                                  use_hierarchical=use_hierarchical, latents=lat, init_images=init_image,
-                                  strength=strength, posterior_eps=eps if sample_posterior else None,
-                                  masks=mask, composite=composite)
-        return self.to_pil(img)[0]
+        return self._generate([audio_path], [text_prompt], num_inference_steps, guidance_scale, seed, use_hierarchical,
+                              init_image, strength, sample_posterior, mask, composite)[0]
 
     def batch_generate(self, audio_paths, text_prompts=None, **kwargs):
         """The reference runs generate(path, prompt, **kwargs) per item (scripts/inference.py:168-180),
         so every item is re-seeded with the same seed (the same initial noise for every item) and
-        seed=None leaves the RNG unseeded; here the items run as one batch with those latents."""
+        seed=None leaves the RNG unseeded; here the items run as one batch with those latents.
+        init_images= and masks= (one per item, or one for all), strength=, sample_posterior=, composite= as
+        generate()."""
         if text_prompts is None:
             text_prompts = [""] * len(audio_paths)
-        steps = kwargs.get("num_inference_steps", 50)
-        g = kwargs.get("guidance_scale", 7.5)
-        seed = kwargs.get("seed", None)
-        mel = self.mel_features([self.load_audio(p) for p in audio_paths])
-        init_images = kwargs.get("init_images", None)
-        masks = kwargs.get("masks", None)   # masks= (one per item, or one for all), composite= as generate()
-        if masks is not None and init_images is None:
-            raise ValueError("masks= needs init_images=: inpainting repaints a region of those images")
-        if init_images is None:
-            img = self.generate_batch(mel, list(text_prompts), steps, g,
-                                      use_hierarchical=kwargs.get("use_hierarchical", True),
-                                      latents=self._request_latents(len(audio_paths), seed))
-            return self.to_pil(img)
-        # init_images= (one per item, or one for all), strength=, sample_posterior= as generate()
-        lat, eps = self._request_latents(len(audio_paths), seed, with_eps=True)
-        img = self.generate_batch(mel, list(text_prompts), steps, g,
-                                  use_hierarchical=kwargs.get("use_hierarchical", True), latents=lat,
-                                  init_images=init_images, strength=kwargs.get("strength", 0.8),
-                                  posterior_eps=eps if kwargs.get("sample_posterior", True) else None,
-                                  masks=masks, composite=kwargs.get("composite", True))
-        return self.to_pil(img)
+        return self._generate(audio_paths, text_prompts, **kwargs)
 
     # ------------------------------------------------------------ batched core
     def initial_latents(self, seeds: list[int]) -> torch.Tensor:
@@ -544,47 +367,31 @@ class AudioToImageInference:
         noised to timesteps[t_start], or `latents` themselves when t_start is 0) and its latent mask; the masked
         step (c2d_cfg_ddim_step_masked) runs steps - t_start times; with composite the kept pixels of the decode are
         set back to the init images' bytes (c2d_composite_u8)."""
-        if masks is not None and init_images is None:
-            raise ValueError("masks= needs init_images=: inpainting repaints a region of those images")
         b = mel.shape[0]
+        req = self._resolve(b, num_inference_steps, init_images, strength, masks, composite)
+        seeds = seeds if seeds is not None else list(range(b))
+        if latents is None and req.images is not None and posterior_eps is None and sample_posterior:
+            latents, posterior_eps = initial_latents_and_eps(seeds, self.height // 8, self.width // 8, self.device)
+        elif latents is None:
+            latents = self.initial_latents(seeds)
+        if req.images is not None and tuple(latents.shape[-2:]) != (self.height // 8, self.width // 8):
+            raise ValueError(f"latents {tuple(latents.shape)} do not match init images {tuple(req.images.shape)}")
         if ids is None:
             ids = (self.tokenizer([""] * b, self.device), self.tokenizer(prompts or [""] * b, self.device))
         ehs, kw, _ = self.condition(mel, ids[0], ids[1], use_hierarchical)
-        t_start = 0
-        if init_images is not None:
-            t_start = DDIMScheduler.img2img_start(num_inference_steps, strength)
-            imgs = self.prepare_images(init_images, b)
-            if masks is not None:
-                masks = self.prepare_masks(masks, b)
-                self._check_masks(masks, imgs)
-            if latents is None and posterior_eps is None and sample_posterior:
-                latents, posterior_eps = initial_latents_and_eps(seeds if seeds is not None else list(range(b)),
-                                                                 self.height // 8, self.width // 8, self.device)
-        if latents is None:
-            latents = self.initial_latents(seeds if seeds is not None else list(range(b)))
         den = self.denoiser(b, num_inference_steps, guidance_scale, ehs, kw, latent_hw=tuple(latents.shape[-2:]))
         den.ehs.copy_(ehs)
         for k, v in kw["audio"].items():
             den.kw["audio"][k].copy_(v)
-        if init_images is None:
-            x = den.run(latents * self.scheduler.init_noise_sigma)
-            return self.vae(x)
-        if tuple(latents.shape[-2:]) != (imgs.shape[1] // 8, imgs.shape[2] // 8):
-            raise ValueError(f"latents {tuple(latents.shape)} do not match init images {tuple(imgs.shape)}")
-        noise = latents.to(self.device, torch.float32).contiguous()
+        moments = self.vae_encoder(req.images) if req.images is not None else None
+        den.prepare_context()
+        masked = req.masks is not None
+        den.ensure_captured(masked)
         eps = posterior_eps.to(self.device, torch.float32).contiguous() if posterior_eps is not None else None
-        den.step_idx.fill_(t_start)   # the kernel reads the alpha of the first step that runs through the counter
-        if masks is not None:
-            den.masked_buffers()
-            # t_start 0 (strength 1): the loop starts from the noise itself (init_noise_sigma is 1 for DDIM)
-            ops.inpaint_prepare(self.vae_encoder(imgs), noise, masks, SCALING, eps=eps, coef=den.coef,
-                                step_index=den.step_idx, pure_noise=t_start == 0, z0=den.z0, x=den.x, mask=den.mask)
-            den.noise.copy_(noise)
-            img = self.vae(den.run(None, start=t_start, masked=True))
-            return ops.composite_u8(img, imgs, masks, out=img) if composite else img
-        x0 = ops.vae_posterior_noise(self.vae_encoder(imgs), torch.empty_like(noise), SCALING, eps=eps, noise=noise,
-                                     coef=den.coef, step_index=den.step_idx)
-        return self.vae(den.run(x0, start=t_start))
+        den.start(latents.to(self.device, torch.float32).contiguous(), req.t_start, moments=moments, eps=eps,
+                  mask_u8=req.masks)
+        img = self.vae(den.denoise(req.t_start, masked))
+        return ops.composite_u8(img, req.images, req.masks, out=img) if req.composite else img
 
     @torch.no_grad()
     def generate_batch_graphed(self, wave: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor,
@@ -606,25 +413,16 @@ class AudioToImageInference:
         conditioning graph then ends with c2d_inpaint_prepare over static image and mask buffers, the steps
         replay the sampler's masked graph, and with composite the decode graph ends with c2d_composite_u8; a
         call with another image or mask copies it into the static buffers and replays the same graphs."""
-        if masks is not None and init_images is None:
-            raise ValueError("masks= needs init_images=: inpainting repaints a region of those images")
-        t_start = 0
-        if init_images is not None:
-            t_start = DDIMScheduler.img2img_start(num_inference_steps, strength)
-            init_images = self.prepare_images(init_images, offsets.numel())
-        if masks is not None:
-            masks = self.prepare_masks(masks, offsets.numel())
-            self._check_masks(masks, init_images)
-        composite = bool(composite) and masks is not None
+        req = self._resolve(offsets.numel(), num_inference_steps, init_images, strength, masks, composite)
         key = (offsets.numel(), wave.numel(), num_inference_steps, float(guidance_scale), tuple(latents.shape),
-               bool(use_hierarchical), slot, masks is not None, composite, t_start, init_images is not None,
+               bool(use_hierarchical), slot, req.masks is not None, req.composite, req.t_start, req.images is not None,
                posterior_eps is not None)
         bg = self._batch_graphs.get(key)
         if bg is None:
             bg = BatchGraph(self, wave, offsets, lengths, ids, latents, num_inference_steps, guidance_scale,
-                            use_hierarchical, slot, init_images, t_start, posterior_eps, masks, composite)
+                            use_hierarchical, slot, req, posterior_eps)
             self._batch_graphs[key] = bg
-        return bg.run(wave, offsets, lengths, ids, latents, init_images, posterior_eps, masks)
+        return bg.run(wave, offsets, lengths, ids, latents, req.images, posterior_eps, req.masks)
 
     @staticmethod
     def to_pil(images: torch.Tensor):
@@ -650,17 +448,13 @@ class BatchGraph:
     c2d_composite_u8 into the static image."""
 
     def __init__(self, pipe: AudioToImageInference, wave, offsets, lengths, ids, latents, steps: int,
-                 guidance: float, use_hierarchical: bool, slot: int = 0, init_images=None, t_start: int = 0,
-                 posterior_eps=None, masks=None, composite: bool = True):
-        self.pipe, self.steps, self.use_hier = pipe, steps, use_hierarchical
-        self.t_start = t_start
-        if masks is not None and init_images is None:
-            raise ValueError("masks need init images")
-        self.masks = masks.clone() if masks is not None else None
-        self.composite = bool(composite) and masks is not None
-        self.images = init_images.clone() if init_images is not None else None
+                 guidance: float, use_hierarchical: bool, slot: int, req: _Request, posterior_eps=None):
+        self.pipe, self.use_hier = pipe, use_hierarchical
+        self.t_start, self.composite = req.t_start, req.composite
+        self.masks = req.masks.clone() if req.masks is not None else None
+        self.images = req.images.clone() if req.images is not None else None
         self.eps = posterior_eps.float().clone() if posterior_eps is not None else None
-        self.enc = pipe.vae_encoder if init_images is not None else None
+        self.enc = pipe.vae_encoder if self.images is not None else None
         self.wave, self.offs, self.lens = wave.clone(), offsets.clone(), lengths.clone()
         self.ids_u, self.ids_c = ids[0].clone(), ids[1].clone()
         self.lat = latents.float().clone()
@@ -673,12 +467,7 @@ class BatchGraph:
         self.den = pipe.denoiser(b, steps, guidance, ehs, kw, latent_hw=tuple(self.lat.shape[-2:]), slot=slot)
         self.den.ehs.copy_(ehs)
         self.den.prepare_context()
-        if self.den.use_graph and self.den.graph is None:
-            self.den.capture()
-        if self.masks is not None:
-            self.den.masked_buffers()
-            if self.den.use_graph and self.den.graph_masked is None:
-                self.den.capture_masked()
+        self.den.ensure_captured(self.masks is not None)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -706,19 +495,8 @@ class BatchGraph:
         for k, v in kw["audio"].items():
             den.kw["audio"][k].copy_(v)
         den.prepare_context()
-        if self.images is None:
-            den.x.copy_(self.lat * pipe.scheduler.init_noise_sigma)
-            den.step_idx.zero_()
-            return
-        den.step_idx.fill_(self.t_start)
-        if self.masks is not None:
-            ops.inpaint_prepare(self.enc(self.images), self.lat, self.masks, SCALING, eps=self.eps, coef=den.coef,
-                                step_index=den.step_idx, pure_noise=self.t_start == 0, z0=den.z0, x=den.x,
-                                mask=den.mask)
-            den.noise.copy_(self.lat)
-            return
-        ops.vae_posterior_noise(self.enc(self.images), den.x, SCALING, eps=self.eps, noise=self.lat, coef=den.coef,
-                                step_index=den.step_idx)
+        moments = self.enc(self.images) if self.images is not None else None
+        den.start(self.lat, self.t_start, moments=moments, eps=self.eps, mask_u8=self.masks)
 
     def run(self, wave, offsets, lengths, ids, latents, init_images=None, posterior_eps=None,
             masks=None) -> torch.Tensor:
@@ -734,11 +512,7 @@ class BatchGraph:
             if src.data_ptr() != dst.data_ptr():
                 dst.copy_(src)
         self.g_cond.replay()
-        for _ in range(self.steps - self.t_start):
-            if self.masks is not None:
-                self.den.step_masked()
-            else:
-                self.den.graph.replay() if self.den.use_graph else self.den._body()
+        self.den.denoise(self.t_start, self.masks is not None)
         self.g_vae.replay()
         self.pipe.last_denoiser = self.den
         return self.img

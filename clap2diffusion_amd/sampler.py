@@ -24,6 +24,7 @@ import torch
 
 from . import ops
 from .scheduler import DDIMScheduler
+from .vae import SCALING
 
 
 class GraphDenoiser:
@@ -92,68 +93,80 @@ class GraphDenoiser:
         else:
             ops.cfg_ddim_step(eps, self.x, self.g, self.coef, self.step_idx, advance=True)
 
-    def capture(self) -> None:
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._body()  # warm-up: packs lazily-built weights, primes the allocator
-        torch.cuda.current_stream().wait_stream(s)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self._body()
-        self.step_idx.zero_()
-
-    def capture_masked(self) -> None:
-        """The masked body as a second graph; self.graph stays as it is.  It is captured into the first graph's
-        memory pool: the two bodies allocate the same UNet activations, neither reads anything the other left
-        there (all state is in the static buffers), and one stream replays them one after the other, so the
-        activations are held once."""
-        self.masked_buffers()
-        if self.graph is None:
-            self.capture()
+    def _capture(self, masked: bool, pool=None) -> torch.cuda.CUDAGraph:
         self.step_idx.zero_()   # the warm-up below runs the step kernel: keep the counter inside the table
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            self._body(masked=True)
+            self._body(masked)  # warm-up: packs lazily-built weights, primes the allocator
         torch.cuda.current_stream().wait_stream(s)
-        self.graph_masked = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph_masked, pool=self.graph.pool()):
-            self._body(masked=True)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, pool=pool):
+            self._body(masked)
         self.step_idx.zero_()
+        return graph
 
-    def step_masked(self) -> None:
-        """One masked step: a replay of the masked graph, or the eager body."""
-        self.graph_masked.replay() if self.use_graph else self._body(masked=True)
+    def ensure_captured(self, masked: bool = False) -> None:
+        """Capture the step graph, and for a masked run the masked buffers and graph, on their first use.  The
+        warm-up and the recorded step run on x, so call this before start().  The masked body is a second graph;
+        self.graph stays as it is.  It is captured into the first graph's memory pool: the two bodies allocate the
+        same UNet activations, neither reads anything the other left there (all state is in the static buffers),
+        and one stream replays them one after the other, so the activations are held once."""
+        if masked:
+            self.masked_buffers()
+        if not self.use_graph:
+            return
+        if self.graph is None:
+            self.graph = self._capture(False)
+        if masked and self.graph_masked is None:
+            self.graph_masked = self._capture(True, pool=self.graph.pool())
+
+    def start(self, latents: torch.Tensor, t_start: int = 0, moments: torch.Tensor | None = None,
+              eps: torch.Tensor | None = None, mask_u8: torch.Tensor | None = None) -> None:
+        """Write the state the loop starts from: x, the device step counter and, with a mask, z0 / noise / mask.
+        latents fp32 [B, 4, h, w] on the device, contiguous: the initial noise.  No host synchronisation, so a
+        caller may record it into a graph.
+        moments None (text-to-image): x = latents * init_noise_sigma, counter 0.
+        moments (the VAE encoder's fp16 rows of the init images; img2img): x = the posterior sample (eps fp32, None:
+        the mode) noised with latents to timesteps[t_start]; the kernel reads that step's alpha through the counter.
+        mask_u8 uint8 [B, 8h, 8w] as well (inpainting): one launch writes z0, x (latents themselves when t_start is
+        0: strength 1 starts from pure noise, init_noise_sigma is 1 for DDIM) and the latent mask."""
+        if not 0 <= t_start < self.steps:
+            raise ValueError(f"t_start {t_start} outside [0, {self.steps})")
+        if moments is None and (t_start or mask_u8 is not None):
+            raise ValueError("t_start and mask_u8 need the init image's moments")
+        if moments is None:
+            self.x.copy_(latents * self.sched.init_noise_sigma)
+            self.step_idx.zero_()
+        elif mask_u8 is None:
+            self.step_idx.fill_(t_start)
+            ops.vae_posterior_noise(moments, self.x, SCALING, eps=eps, noise=latents, coef=self.coef,
+                                    step_index=self.step_idx)
+        else:
+            self.masked_buffers()
+            self.step_idx.fill_(t_start)
+            ops.inpaint_prepare(moments, latents, mask_u8, SCALING, eps=eps, coef=self.coef, step_index=self.step_idx,
+                                pure_noise=t_start == 0, z0=self.z0, x=self.x, mask=self.mask)
+            self.noise.copy_(latents)
+
+    def step(self, masked: bool = False) -> None:
+        """One step: a replay of the (masked) step graph, or the eager body."""
+        if self.use_graph:
+            (self.graph_masked if masked else self.graph).replay()
+        else:
+            self._body(masked)
+
+    def denoise(self, t_start: int = 0, masked: bool = False) -> torch.Tensor:
+        """The loop: steps - t_start steps from the state start() wrote -> denoised latents fp32 (self.x)."""
+        for _ in range(self.steps - t_start):
+            self.step(masked)
+        return self.x
 
     @torch.no_grad()
-    def run(self, latents: torch.Tensor | None, start: int = 0, masked: bool = False) -> torch.Tensor:
-        """latents [B,4,h,w] (scaled by init_noise_sigma = 1) -> denoised latents fp32.
-        start: first step index (img2img: latents already noised to timesteps[start]); the device counter is
-        set to it and the same captured step is replayed steps - start times.
-        masked (inpainting): self.z0 / self.noise / self.mask / self.x are already filled (ops.inpaint_prepare;
-        latents is not read) and the masked step runs steps - start times."""
-        if not 0 <= start < self.steps:
-            raise ValueError(f"start {start} outside [0, {self.steps})")
+    def run(self, latents: torch.Tensor, t_start: int = 0, moments: torch.Tensor | None = None,
+            eps: torch.Tensor | None = None, mask_u8: torch.Tensor | None = None) -> torch.Tensor:
+        """start()'s arguments -> denoised latents fp32: the whole run of one denoiser on its own."""
         self.prepare_context()
-        if masked:
-            if self.z0 is None:
-                raise RuntimeError("masked run before masked_buffers(): z0 / noise / mask / x are not filled")
-            if self.use_graph and self.graph_masked is None:
-                x = self.x.clone()      # the capture's warm-up and the step it records run on x
-                self.capture_masked()
-                self.x.copy_(x)
-            self.step_idx.fill_(start)
-            for _ in range(self.steps - start):
-                self.step_masked()
-            return self.x
-        if self.use_graph and self.graph is None:
-            self.capture()
-        self.x.copy_(latents)
-        self.step_idx.fill_(start)
-        for _ in range(self.steps - start):
-            if self.use_graph:
-                self.graph.replay()
-            else:
-                self._body()
-        return self.x
+        self.ensure_captured(mask_u8 is not None)
+        self.start(latents, t_start, moments, eps, mask_u8)
+        return self.denoise(t_start, mask_u8 is not None)

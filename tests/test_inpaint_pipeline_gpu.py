@@ -275,6 +275,25 @@ def test_batch_graph_matches_eager_and_follows_image_and_mask(pipe, request_inpu
     assert all(k[-2] for k in masked_keys(pipe))             # the key still ends (init image, posterior eps)
 
 
+def test_eager_body_matches_graph_replay_in_every_mode(pipe, request_inputs, dev):
+    """A use_graph=False pipeline (every step the sampler's eager body, nothing captured) against the graphed `pipe`
+    in text-to-image, img2img and inpainting.  Bar: bit equality of the images and the final latents; the body and
+    its replay launch the same kernels on the same static buffers, and were measured bit-identical in all three
+    modes at this size."""
+    _, mel, ids, noise, img = request_inputs
+    body = AudioToImageInference(device=dev, height=SIZE, width=SIZE, verbose=False, use_graph=False)
+    modes = {"text-to-image": {}, "img2img": dict(init_images=img, strength=0.5),
+             "inpaint": dict(init_images=img, strength=0.5, masks=partial_mask().to(dev))}
+    for name, kw in modes.items():
+        kw = dict(kw, ids=ids, latents=noise, sample_posterior=False)
+        got = body.generate_batch(mel, None, STEPS, GUIDANCE, **kw)
+        assert body.last_denoiser.graph is None and body.last_denoiser.graph_masked is None
+        want = pipe.generate_batch(mel, None, STEPS, GUIDANCE, **kw)
+        assert pipe.last_denoiser.graph is not None
+        assert torch.equal(got, want), name
+        assert torch.equal(body.last_denoiser.x, pipe.last_denoiser.x), name
+
+
 def test_seed_fixes_both_noises(pipe, request_inputs):
     _, _, _, _, img = request_inputs
     kw = dict(text_prompt="a beach", num_inference_steps=STEPS, init_image=img[:1], strength=0.5,
