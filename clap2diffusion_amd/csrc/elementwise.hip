@@ -338,11 +338,188 @@ __global__ void inpaint_prepare_kernel(const f16* __restrict__ mom, int ld, cons
     mask[i] = mask_u8[(bi * 8 * h + 8 * yo) * 8 * w + 8 * xo] >= 128 ? 1.0f : 0.0f;
 }
 
+// ---- CLIP image preprocess: uint8 image -> normalised fp16 patch rows (c2d_clip_preprocess, c2d.h) ----
+// PIL's bicubic kernel (ImagingResample, a = -0.5)
+__device__ __forceinline__ float pil_cubic(float x) {
+    const float A = -0.5f;
+    x = fabsf(x);
+    if (x < 1.0f) return ((A + 2.0f) * x - (A + 3.0f)) * x * x + 1.0f;
+    if (x < 2.0f) return (((x - 5.0f) * x + 8.0f) * x - 4.0f) * A;
+    return 0.0f;
+}
+
+// a pass's stored byte: floor(v + 0.5) clamped to [0, 255]
+__device__ __forceinline__ float round_u8(float v) { return fminf(fmaxf(floorf(v + 0.5f), 0.0f), 255.0f); }
+
+constexpr int kClipMaxPatch = 32;    // patch side: the per-patch tables and the staged row are static LDS
+constexpr int kClipChunkRows = 64;   // source rows per horizontal-pass chunk held in LDS
+
+struct ClipPre {
+    int h, w;            // source image
+    int top, left;       // the crop window's origin in the resized image
+    int size, patch, kpad;
+    double sx, sy;       // n_in / n_out per axis
+    float mean[3], inv_std[3];
+};
+
+// One workgroup per (image, patch).  Both passes touch only what this patch's patch x patch outputs need:
+//   tables      per output column / row of the patch: the tap range [lo, hi), the centre (double: tap offsets of
+//               large images lose bits in fp32) and 1 / (sum of the tap weights); ranges and centres in double with
+//               contraction off, the operations of the float64 statement in c2d.h
+//   horizontal  source rows [ylo[0], yhi[patch - 1]) in chunks of kClipChunkRows: each (row, column, channel)
+//               reads its taps from the image (bytes, channel-interleaved: the lanes of a wave read neighbouring
+//               bytes) and stores the rounded byte in LDS
+//   vertical    each output element adds its taps of the chunk to its fp32 accumulator (LDS; an element is always
+//               visited by the same thread, so the accumulators need no barrier of their own)
+//   store       round, normalise, fp16 into the staged row (zero-filled to kpad), then 16-byte stores
+// No load leaves the image: tap ranges are clipped to [0, n_in) and chunk rows to yhi[patch - 1] <= h.
+__global__ void __launch_bounds__(256) clip_preprocess_kernel(const uint8_t* __restrict__ img, ClipPre a,
+                                                              f16* __restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ double s_c[2][kClipMaxPatch];
+    __shared__ int s_lo[2][kClipMaxPatch], s_hi[2][kClipMaxPatch];
+    __shared__ float s_inv[2][kClipMaxPatch];
+    __shared__ float s_acc[3 * kClipMaxPatch * kClipMaxPatch];
+    __shared__ uint8_t s_t[kClipChunkRows * kClipMaxPatch * 3];
+    __shared__ __attribute__((aligned(16))) f16 s_row[(3 * kClipMaxPatch * kClipMaxPatch + 63) / 64 * 64];
+
+    const int P = a.patch, g = a.size / P, tid = threadIdx.x;
+    const size_t blk = blockIdx.x;
+    const int pidx = (int)(blk % (size_t)(g * g));
+    const size_t bi = blk / (size_t)(g * g);
+    const int py = pidx / g, px = pidx - py * g;
+    const float inv_fx = 1.0f / (float)fmax(a.sx, 1.0), inv_fy = 1.0f / (float)fmax(a.sy, 1.0);
+
+    if (tid < 2 * P) {
+        const int axis = tid / P, i = tid - axis * P;   // 0: columns, 1: rows
+        const int n_in = axis ? a.h : a.w;
+        const int o = (axis ? a.top + py * P : a.left + px * P) + i;
+        const double scale = axis ? a.sy : a.sx;
+        const double fs = fmax(scale, 1.0), support = 2.0 * fs;
+        const double centre = ((double)o + 0.5) * scale;
+        const int lo = max((int)(centre - support + 0.5), 0);
+        const int hi = min((int)(centre + support + 0.5), n_in);
+        const float inv_f = axis ? inv_fy : inv_fx;
+        float sum = 0.0f;
+        for (int j = lo; j < hi; ++j) sum += pil_cubic((float)((double)j + 0.5 - centre) * inv_f);
+        s_c[axis][i] = centre;
+        s_lo[axis][i] = lo;
+        s_hi[axis][i] = hi;
+        s_inv[axis][i] = 1.0f / sum;
+    }
+    const int n_out = 3 * P * P;
+    for (int e = tid; e < n_out; e += 256) s_acc[e] = 0.0f;
+    __syncthreads();
+
+    const int y0 = s_lo[1][0], y1 = s_hi[1][P - 1];
+    const uint8_t* src = img + bi * (size_t)a.h * a.w * 3;
+    for (int r0 = y0; r0 < y1; r0 += kClipChunkRows) {
+        const int nr = min(kClipChunkRows, y1 - r0);
+        for (int idx = tid; idx < nr * P * 3; idx += 256) {
+            const int c = idx % 3, x = (idx / 3) % P, jr = idx / (3 * P);
+            const uint8_t* row = src + (size_t)(r0 + jr) * a.w * 3 + c;
+            const double cx = s_c[0][x];
+            float s = 0.0f;
+            for (int i = s_lo[0][x]; i < s_hi[0][x]; ++i)
+                s += pil_cubic((float)((double)i + 0.5 - cx) * inv_fx) * (float)row[(size_t)i * 3];
+            s_t[idx] = (uint8_t)round_u8(s * s_inv[0][x]);
+        }
+        __syncthreads();
+        for (int e = tid; e < n_out; e += 256) {
+            const int c = e % 3, dx = (e / 3) % P, dy = e / (3 * P);
+            const int lo = max(s_lo[1][dy], r0), hi = min(s_hi[1][dy], r0 + nr);
+            const double cy = s_c[1][dy];
+            float s = s_acc[e];
+            for (int j = lo; j < hi; ++j)
+                s += pil_cubic((float)((double)j + 0.5 - cy) * inv_fy) * (float)s_t[((j - r0) * P + dx) * 3 + c];
+            s_acc[e] = s;
+        }
+        __syncthreads();
+    }
+
+    for (int e = tid; e < a.kpad; e += 256) {
+        float v = 0.0f;
+        if (e < n_out) {
+            const int c = e % 3, dy = e / (3 * P);
+            v = (round_u8(s_acc[e] * s_inv[1][dy]) / 255.0f - a.mean[c]) * a.inv_std[c];
+        }
+        s_row[e] = (f16)v;
+    }
+    __syncthreads();
+    f16x8* dst = reinterpret_cast<f16x8*>(out + blk * (size_t)a.kpad);
+    for (int q = tid; q < a.kpad / 8; q += 256) dst[q] = reinterpret_cast<const f16x8*>(s_row)[q];
+}
+
+// out[i] = a_i . b_i / max(|a_i| |b_i|, 1e-12): one workgroup per row pair, fp32 sums
+__global__ void __launch_bounds__(256) cosine_rows_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                          int c, float* __restrict__ out) {
+    const size_t row = blockIdx.x;
+    __shared__ float part[3][4];
+    float ab = 0.f, aa = 0.f, bb = 0.f;
+    for (int j = threadIdx.x; j < c; j += blockDim.x) {
+        const float x = a[row * c + j], y = b[row * c + j];
+        ab += x * y;
+        aa += x * x;
+        bb += y * y;
+    }
+    ab = wave_sum(ab);
+    aa = wave_sum(aa);
+    bb = wave_sum(bb);
+    if ((threadIdx.x & 63) == 0) {
+        part[0][threadIdx.x >> 6] = ab;
+        part[1][threadIdx.x >> 6] = aa;
+        part[2][threadIdx.x >> 6] = bb;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float d = part[0][0] + part[0][1] + part[0][2] + part[0][3];
+        const float na = sqrtf(part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+        const float nb = sqrtf(part[2][0] + part[2][1] + part[2][2] + part[2][3]);
+        out[row] = d / fmaxf(na * nb, 1e-12f);
+    }
+}
+
 }  // namespace c2d
 
 using namespace c2d;
 
 extern "C" const char* c2d_version(void) { return "c2d_hip gfx950 r7"; }
+
+extern "C" int c2d_clip_preprocess(const uint8_t* img, int n, int h, int w, int size, int patch, const float* mean,
+                                   const float* std, int kpad, void* out, void* stream) {
+    if (!img || !mean || !std || !out) return C2D_E_ARG;
+    if (n <= 0 || h <= 0 || w <= 0 || size <= 0 || patch <= 0 || patch > kClipMaxPatch || size % patch) return C2D_E_SHAPE;
+    if (kpad != (3 * patch * patch + 63) / 64 * 64) return C2D_E_SHAPE;
+    for (int c = 0; c < 3; ++c)
+        if (!(std[c] > 0.0f)) return C2D_E_ARG;
+    const long long g = size / patch, blocks = (long long)n * g * g;
+    // the longer resized side, int(size * long / short), must stay an int
+    const long long lng = (long long)size * (h > w ? h : w) / (h > w ? w : h);
+    if (blocks > INT32_MAX || lng > INT32_MAX) return C2D_E_SHAPE;
+    if (!aligned16(out)) return C2D_E_ALIGN;
+    ClipPre a;
+    a.h = h; a.w = w; a.size = size; a.patch = patch; a.kpad = kpad;
+    const int rh = h <= w ? size : (int)lng, rw = h <= w ? (int)lng : size;   // shorter side -> size
+    a.top = (rh - size) / 2;
+    a.left = (rw - size) / 2;
+    a.sy = (double)h / (double)rh;
+    a.sx = (double)w / (double)rw;
+    for (int c = 0; c < 3; ++c) {
+        a.mean[c] = mean[c];
+        a.inv_std[c] = 1.0f / std[c];
+    }
+    hipLaunchKernelGGL(clip_preprocess_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, img, a,
+                       (f16*)out);
+    return check_launch();
+}
+
+extern "C" int c2d_cosine_rows(const float* a, const float* b, int m, int c, float* out, void* stream) {
+    if (!a || !b || !out) return C2D_E_ARG;
+    if (m <= 0 || c <= 0) return C2D_E_SHAPE;
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 3) return C2D_E_ALIGN;
+    hipLaunchKernelGGL(cosine_rows_kernel, dim3(m), dim3(256), 0, (hipStream_t)stream, a, b, c, out);
+    return check_launch();
+}
 
 extern "C" int c2d_timestep_embedding(const float* t_table, const int* step_index, int n, int dim, void* out,
                                       void* stream) {

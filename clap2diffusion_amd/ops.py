@@ -481,6 +481,40 @@ def l2_normalize_(x: torch.Tensor) -> torch.Tensor:
     return x
 
 
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)   # OpenAI CLIP's image_mean / image_std (CLIPImageProcessor)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+def clip_preprocess(images_u8: torch.Tensor, size: int = 224, patch: int = 14, mean=CLIP_MEAN, std=CLIP_STD,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
+    """uint8 [B, H, W, 3] (any H, W) -> fp16 [B * (size / patch)^2, kpad_of(3 * patch^2)]: CLIPImageProcessor in one
+    launch (c2d::clip_preprocess): PIL-bicubic resize of the shorter side to `size`, centre crop, (v / 255 - mean) /
+    std, and the patch cut with K ordered (dy, dx, channel) as pack_conv_weight orders a patch x patch conv."""
+    _require(images_u8, "images_u8")
+    assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3
+    assert images_u8.is_contiguous()
+    if size <= 0 or patch <= 0 or size % patch:
+        raise ValueError(f"size {size} is no positive multiple of patch {patch}")
+    rows, kp = images_u8.shape[0] * (size // patch) ** 2, kpad_of(3 * patch * patch)
+    if out is None:
+        out = torch.empty((rows, kp), device=images_u8.device, dtype=F16)
+    assert out.dtype == F16 and out.is_contiguous() and tuple(out.shape) == (rows, kp)
+    C2D.clip_preprocess(images_u8, int(size), int(patch), [float(v) for v in mean], [float(v) for v in std], out)
+    return out
+
+
+def cosine_rows(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """fp32 [M, C] row pairs -> fp32 [M]: a_i . b_i / max(|a_i| |b_i|, 1e-12) (c2d::cosine_rows)."""
+    _require(a, "a")
+    assert a.dim() == 2 and a.shape == b.shape and b.is_cuda
+    assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
+    if out is None:
+        out = torch.empty((a.shape[0],), device=a.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (a.shape[0],)
+    C2D.cosine_rows(a, b, out)
+    return out
+
+
 def timestep_embedding(t_table: torch.Tensor, step_index: torch.Tensor | None, n: int, dim: int) -> torch.Tensor:
     out = torch.empty((n, dim), device=t_table.device, dtype=F16)
     C2D.timestep_embedding(t_table, step_index, n, dim, out)

@@ -276,17 +276,21 @@ class AudioToImageInference:
         return torch.cat(lat).to(self.device), torch.cat(eps).to(self.device) if with_eps else None
 
     @torch.no_grad()
-    def _generate(self, audio_paths, text_prompts, num_inference_steps=50, guidance_scale=7.5, seed=None,
-                  use_hierarchical=True, init_images=None, strength=0.8, sample_posterior=True, masks=None,
-                  composite=True, **_):
-        """generate() for a list of requests -> PIL images; keywords it does not know are ignored."""
+    def _generate_u8(self, audio_paths, text_prompts, num_inference_steps=50, guidance_scale=7.5, seed=None,
+                     use_hierarchical=True, init_images=None, strength=0.8, sample_posterior=True, masks=None,
+                     composite=True, **_):
+        """generate() for a list of requests -> generate_batch's uint8 [B, H, W, 3] device tensor; keywords it does
+        not know are ignored."""
         mel = self.mel_features([self.load_audio(p) for p in audio_paths])
         lat, eps = self._request_latents(len(audio_paths), seed, with_eps=init_images is not None)
-        img = self.generate_batch(mel, list(text_prompts), num_inference_steps, guidance_scale,
-                                  use_hierarchical=use_hierarchical, latents=lat, init_images=init_images,
-                                  strength=strength, posterior_eps=eps if sample_posterior else None, masks=masks,
-                                  composite=composite)
-        return self.to_pil(img)
+        return self.generate_batch(mel, list(text_prompts), num_inference_steps, guidance_scale,
+                                   use_hierarchical=use_hierarchical, latents=lat, init_images=init_images,
+                                   strength=strength, posterior_eps=eps if sample_posterior else None, masks=masks,
+                                   composite=composite)
+
+    def _generate(self, audio_paths, text_prompts, *args, **kwargs):
+        """_generate_u8 -> PIL images."""
+        return self.to_pil(self._generate_u8(audio_paths, text_prompts, *args, **kwargs))
 
     def generate(self, audio_path, text_prompt="", num_inference_steps=50, guidance_scale=7.5, seed=None,
                  use_hierarchical=True, init_image=None, strength=0.8, sample_posterior=True, mask=None,
@@ -307,9 +311,14 @@ class AudioToImageInference:
         seed=None leaves the RNG unseeded; here the items run as one batch with those latents.
         init_images= and masks= (one per item, or one for all), strength=, sample_posterior=, composite= as
         generate()."""
+        return self.to_pil(self.batch_generate_u8(audio_paths, text_prompts, **kwargs))
+
+    def batch_generate_u8(self, audio_paths, text_prompts=None, **kwargs) -> torch.Tensor:
+        """batch_generate without the copy to the host: the images as generate_batch leaves them, uint8
+        [B, H, W, 3] on the device (what the evaluator scores)."""
         if text_prompts is None:
             text_prompts = [""] * len(audio_paths)
-        return self._generate(audio_paths, text_prompts, **kwargs)
+        return self._generate_u8(audio_paths, text_prompts, **kwargs)
 
     # ------------------------------------------------------------ batched core
     def initial_latents(self, seeds: list[int]) -> torch.Tensor:

@@ -329,6 +329,23 @@ def inpaint_prepare(moments: Tensor, eps: Optional[Tensor], noise: Tensor, mask_
                                     stream_ptr()), "c2d_inpaint_prepare")
 
 
+@custom_op("c2d::clip_preprocess", mutates_args=("out",), device_types=_CU)
+def clip_preprocess(img: Tensor, size: int, patch: int, mean: list[float], std: list[float], out: Tensor) -> None:
+    """c2d_clip_preprocess: uint8 [n][h][w][3] -> fp16 [n * (size / patch)^2][kpad] normalised patch rows (PIL
+    bicubic resize of the shorter side to `size`, centre crop, (v / 255 - mean) / std, patch cut)."""
+    n, h, w, _ = img.shape
+    f3 = ctypes.c_float * 3
+    check(lib().c2d_clip_preprocess(ptr(img), n, h, w, size, patch, f3(*mean), f3(*std), out.shape[1], ptr(out),
+                                    stream_ptr()), "c2d_clip_preprocess")
+
+
+@custom_op("c2d::cosine_rows", mutates_args=("out",), device_types=_CU)
+def cosine_rows(a: Tensor, b: Tensor, out: Tensor) -> None:
+    """c2d_cosine_rows: fp32 [m][c] row pairs -> out fp32 [m], a_i . b_i / max(|a_i| |b_i|, 1e-12)."""
+    m, c = a.shape
+    check(lib().c2d_cosine_rows(ptr(a), ptr(b), m, c, ptr(out), stream_ptr()), "c2d_cosine_rows")
+
+
 @custom_op("c2d::upsample_nearest2x", mutates_args=("out",), device_types=_CU)
 def upsample_nearest2x(x: Tensor, out: Tensor) -> None:
     n, h, w, c = x.shape
@@ -344,7 +361,8 @@ def add(a: Tensor, b: Tensor, out: Tensor) -> None:
 for _op in (pack_weights, groupnorm_stats, groupnorm_apply, groupnorm, groupnorm_pad, groupnorm_moments, layernorm_stats, layernorm, attention_fwd,
             attention_small, window_attention, htsat_mel_patches, patch_merge_gather, row_mean, softmax_rows,
             l2_normalize, clap_log_mel, timestep_embedding, cfg_ddim_step, latent_to_nhwc, upsample_nearest2x, add,
-            image_to_nhwc, vae_posterior_noise, cfg_ddim_step_masked, mask_to_latent, composite_u8, inpaint_prepare):
+            image_to_nhwc, vae_posterior_noise, cfg_ddim_step_masked, mask_to_latent, composite_u8, inpaint_prepare,
+            clip_preprocess, cosine_rows):
     _op.register_fake(lambda *args, **kwargs: None)
 
 OPS = ("conv2d_igemm", "pack_weights", "groupnorm_stats", "groupnorm_apply", "groupnorm", "groupnorm_pad", "groupnorm_moments",
@@ -352,4 +370,5 @@ OPS = ("conv2d_igemm", "pack_weights", "groupnorm_stats", "groupnorm_apply", "gr
        "layernorm", "attention_fwd", "attention_small", "window_attention", "htsat_mel_patches", "patch_merge_gather",
        "row_mean", "softmax_rows", "l2_normalize", "clap_log_mel", "timestep_embedding", "cfg_ddim_step",
        "latent_to_nhwc", "upsample_nearest2x", "add", "image_to_nhwc", "vae_posterior_noise",
-       "cfg_ddim_step_masked", "mask_to_latent", "composite_u8", "inpaint_prepare")
+       "cfg_ddim_step_masked", "mask_to_latent", "composite_u8", "inpaint_prepare",
+       "clip_preprocess", "cosine_rows")

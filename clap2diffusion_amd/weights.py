@@ -571,6 +571,88 @@ def synth_clip_text(seed: int = 0, device="cpu") -> "OrderedDict[str, torch.Tens
     return sd
 
 
+# ------------------------------------------------------------------ CLIP vision tower / CLIPModel
+CLIP_VISION_CFG = dict(width=1024, layers=24, heads=16, mlp=4096, image=224, patch=14, proj=768)
+
+
+def clip_vision_param_shapes(cfg: dict = CLIP_VISION_CFG) -> "OrderedDict[str, tuple]":
+    """The vision half of a transformers CLIPModel state dict (modeling_clip.py CLIPVisionTransformer,
+    "vision_model." prefix; pre_layrnorm is transformers' own spelling) and visual_projection.weight."""
+    S: "OrderedDict[str, tuple]" = OrderedDict()
+    t, w, f, p = "vision_model.", cfg["width"], cfg["mlp"], cfg["patch"]
+    S[t + "embeddings.class_embedding"] = (w,)
+    S[t + "embeddings.patch_embedding.weight"] = (w, 3, p, p)
+    S[t + "embeddings.position_embedding.weight"] = ((cfg["image"] // p) ** 2 + 1, w)
+    S[t + "pre_layrnorm.weight"] = (w,)
+    S[t + "pre_layrnorm.bias"] = (w,)
+    for i in range(cfg["layers"]):
+        b = f"{t}encoder.layers.{i}."
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            S[f"{b}self_attn.{n}.weight"] = (w, w)
+            S[f"{b}self_attn.{n}.bias"] = (w,)
+        S[b + "layer_norm1.weight"] = (w,)
+        S[b + "layer_norm1.bias"] = (w,)
+        S[b + "mlp.fc1.weight"] = (f, w)
+        S[b + "mlp.fc1.bias"] = (f,)
+        S[b + "mlp.fc2.weight"] = (w, f)
+        S[b + "mlp.fc2.bias"] = (w,)
+        S[b + "layer_norm2.weight"] = (w,)
+        S[b + "layer_norm2.bias"] = (w,)
+    S[t + "post_layernorm.weight"] = (w,)
+    S[t + "post_layernorm.bias"] = (w,)
+    S["visual_projection.weight"] = (cfg["proj"], w)
+    return S
+
+
+def synth_clip_shapes(shapes, seed: int, device) -> "OrderedDict[str, torch.Tensor]":
+    """synth_clip_text's recipe over any CLIP key set: embeddings N(0, 0.02^2), linears N(0, 1 / fan_in),
+    LayerNorm gamma 1 + 0.1 N and beta 0.1 N, other biases 0.02 N."""
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    g = torch.Generator(device=device)
+    for k, shp in shapes.items():
+        g.manual_seed(key_seed(seed, "clip." + k))
+        r = torch.randn(shp, generator=g, device=device)
+        if "embedding" in k:
+            v = 0.02 * r
+        elif "norm" in k:
+            v = (1.0 + 0.1 * r) if k.endswith(".weight") else 0.1 * r
+        elif k.endswith(".bias"):
+            v = 0.02 * r
+        else:
+            v = r / math.sqrt(shp[1])
+        sd[k] = v
+    return sd
+
+
+def synth_clip_vision(seed: int = 0, cfg: dict = CLIP_VISION_CFG, device="cpu") -> "OrderedDict[str, torch.Tensor]":
+    """Seeded CLIP vision tower with its projection (clip_vision_param_shapes keys), synth_clip_text's recipe."""
+    return synth_clip_shapes(clip_vision_param_shapes(cfg), seed, device)
+
+
+def synth_clip_model(seed: int = 0, device="cpu") -> "OrderedDict[str, torch.Tensor]":
+    """Seeded transformers CLIPModel state dict at ViT-L/14: text_model.* (synth_clip_text, the same tensors the
+    pipeline's seeded text encoder holds), vision_model.*, visual_projection.weight, text_projection.weight and
+    logit_scale (CLIP's initial ln(1 / 0.07))."""
+    sd = synth_clip_text(seed, device)
+    sd.update(synth_clip_vision(seed, CLIP_VISION_CFG, device))
+    sd.update(synth_clip_shapes({"text_projection.weight": (CLIP_VISION_CFG["proj"], CLIP_TEXT_CFG["width"])}, seed, device))
+    sd["logit_scale"] = torch.tensor(math.log(1 / 0.07), device=device)
+    return sd
+
+
+def load_clip_model(path) -> dict:
+    """A transformers CLIPModel state dict (text_model.*, vision_model.*, the two projections) from a model folder
+    (model.safetensors / pytorch_model.bin) or a weights file."""
+    from pathlib import Path
+    p = Path(path)
+    sd = load_weights_file(find_weights_file(p, ("model", "pytorch_model")) if p.is_dir() else p)
+    for k in ("vision_model.embeddings.class_embedding", "visual_projection.weight", "text_projection.weight",
+              "text_model.final_layer_norm.weight"):
+        if k not in sd:
+            raise KeyError(f"{p}: no CLIPModel key {k}")
+    return sd
+
+
 def fill_module(module, tag: str, seed: int = 0, keep=("decomposer.temperature", "decomposer.level_prior")):
     """Deterministically (re)initialise every floating tensor of a torch module by key."""
     sd = module.state_dict()

@@ -539,6 +539,41 @@ int c2d_inpaint_prepare(const void* moments, int ld, const float* eps, const flo
                         const float* coef, const int* step_index, int pure_noise, int n, int h, int w,
                         float scaling, float* z0, float* x, float* mask, void* stream);
 
+/*
+ * CLIP-score evaluation (two entry points added to the r7 ABI: no struct changed).
+ *
+ * CLIPImageProcessor in one launch: resize (PIL Image.BICUBIC, shorter side to `size`), centre crop size x size,
+ * rescale, normalise and the ViT patch cut.  img uint8 NHWC [n][h][w][3], h and w any positive size; out fp16
+ * [n * (size / patch)^2][kpad], kpad = (3 * patch^2 + 63) / 64 * 64, 16-byte aligned.  Row b * g^2 + py * g + px
+ * (g = size / patch) is patch (py, px) of image b; its column (dy * patch + dx) * 3 + c is channel c of crop pixel
+ * (py * patch + dy, px * patch + dx), the (ky, kx, cin) K order of c2d_pack_weights, so the patch-embedding
+ * Conv2d(3, width, patch, stride patch) weight packs as a ksize = patch conv weight does; columns from 3 * patch^2
+ * up are zero.  The value is (v / 255 - mean[c]) / std[c] rounded to fp16, v the resized byte.  mean and std are
+ * host arrays of 3 floats, read before the call returns.
+ *   geometry  the shorter of (h, w) becomes size, the longer int(size * long / short); the crop starts at
+ *             top = (h_resized - size) / 2, left = (w_resized - size) / 2 (integer division); only the crop
+ *             window is computed
+ *   resize    separable, the horizontal pass first.  Per axis scale = n_in / n_out, fs = max(scale, 1),
+ *             support = 2 fs; output index i has centre = (i + 0.5) scale and the taps j in
+ *             [max(int(centre - support + 0.5), 0), min(int(centre + support + 0.5), n_in)), weighted
+ *             cubic((j + 0.5 - centre) / fs) with a = -0.5 and normalised to sum 1 over the taps inside the image
+ *   rounding  after each pass the value is floor(v + 0.5) clamped to [0, 255], as PIL stores bytes between the
+ *             passes (without it noise images differ from PIL by up to 21 levels)
+ * Tap ranges and centres are computed in double, the sums in fp32: against the float64 statement above every byte
+ * is within one level and an identity resize (h = w = size) is exact.
+ * C2D_E_ARG: a null pointer or std[c] <= 0; C2D_E_SHAPE: n, h, w, size or patch <= 0, patch > 32,
+ * size % patch != 0, kpad not the value above, n * g^2 or the longer resized side above INT32_MAX;
+ * C2D_E_ALIGN: out not 16-byte aligned; all before any launch.
+ */
+int c2d_clip_preprocess(const uint8_t* img, int n, int h, int w, int size, int patch, const float* mean,
+                        const float* std, int kpad, void* out, void* stream);
+
+/* Row-wise cosine of fp32 [m][c] row pairs, fp32 sums, one launch: out[i] = a_i . b_i / max(|a_i| |b_i|, 1e-12),
+ * so a zero row gives 0.  |a_i| and |b_i| are rooted before they are multiplied: elements up to ~1e18.
+ * C2D_E_ARG: a null pointer; C2D_E_SHAPE: m or c <= 0; C2D_E_ALIGN: a pointer not 4-byte aligned; all before
+ * any launch. */
+int c2d_cosine_rows(const float* a, const float* b, int m, int c, float* out, void* stream);
+
 /* Nearest-neighbour x2 upsample of NHWC fp16 [n, h, w, c] -> [n, 2h, 2w, c], c % 8 == 0.
  * Replaces F.interpolate(scale_factor=2.0, mode="nearest") in diffusers Upsample2D
  * (the UNet up path and the VAE decoder). */
