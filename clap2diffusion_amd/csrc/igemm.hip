@@ -965,6 +965,16 @@ void run_splitk_reduce(const IgemmParams& p, hipStream_t s) {
 void run_splitk_reduce(const IgemmParams& p, hipStream_t s);
 #endif
 
+// Split-K of the row-ring tiles (42 / 43 / 44, igemm_pp16r.h): a slice owns whole 64-channel blocks, 9 K steps
+// each.  nkt K steps a slice asked of ncb blocks -> the slices and the steps per slice the kernel runs
+struct RrSlices { int split, nkt; };
+inline RrSlices rr_slices(int ncb, int nkt) {
+    int cbs = (nkt + 8) / 9;
+    if (cbs < 1) cbs = 1;
+    if (cbs > ncb) cbs = ncb;
+    return {(ncb + cbs - 1) / cbs, 9 * cbs};
+}
+
 }  // namespace c2d
 #include "igemm_m32.h"
 #include "igemm_pp16.h"
@@ -1270,8 +1280,8 @@ static bool rr_hint(long M, int kpad, int cout, int rr_id, int& id, int& split) 
 static DmaPlan rr_plan(int id, int nk, int split) {
     const int ncb = nk / 9;
     const int sp = split < 1 ? 1 : (split > ncb ? ncb : split);
-    const int cbs = (ncb + sp - 1) / sp;
-    return {id, (ncb + cbs - 1) / cbs, 9 * cbs};
+    const RrSlices rs = rr_slices(ncb, 9 * ((ncb + sp - 1) / sp));
+    return {id, rs.split, rs.nkt};
 }
 
 // The folded upsample (c2d_conv_desc::up = 2) plans as a 3x3-class conv with K = 4 cin and M = 4 n h w, under
@@ -1471,14 +1481,6 @@ static c2d_conv_desc tail_desc(const c2d_conv_desc* d, int n1) {
     return t;
 }
 
-// split-K workspace of the tail launch (the head runs one slice)
-static size_t tail_ws_bytes(const c2d_conv_desc* d, int n1) {
-    const c2d_conv_desc t = tail_desc(d, n1);
-    const long Mt = (long)t.n * t.oh * t.ow;
-    const DmaPlan tp = plan_for(Mt, t.cout, t.kpad, t.act, pps_eligible(&t), plan_ksize(&t), rr_eligible(&t), panel_eligible(&t));
-    return tp.split > 1 ? (size_t)tp.split * Mt * t.cout * sizeof(float) : 0;
-}
-
 // c2d_conv_desc::up = 2 (folded upsample): what the mode takes; C2D_OK or the code c2d_conv2d_igemm returns
 static int fold_check(const c2d_conv_desc* d) {
     if (!C2D_TUNE_UPFOLD) return C2D_E_SHAPE;
@@ -1507,126 +1509,141 @@ static int pad_mode_check(const c2d_conv_desc* d) {
     return C2D_OK;
 }
 
-extern "C" size_t c2d_conv2d_igemm_workspace_size(const c2d_conv_desc* d) {
-    if (!d || d->ksize < 1 || d->oh <= 0 || d->ow <= 0 || d->n <= 0 || d->cout <= 0 || d->kpad < 64) return 0;
-    if (d->up == 2 && fold_check(d) != C2D_OK) return 0;
-    if (pad_mode_check(d) != C2D_OK) return 0;
-    if (!dma_eligible(d)) return 0;
-    if (d->pro == C2D_PRO_LNFOLD) return 0;   // the panel GEMM, one slice
-    const long M = (long)d->n * d->oh * d->ow;
-    const DmaPlan pl = plan_for(M, d->cout, d->kpad, d->act, pps_eligible(d), plan_ksize(d), rr_eligible(d), panel_eligible(d));
-    if (const int n1 = tail_images(d, pl)) return tail_ws_bytes(d, n1);
-    return pl.split > 1 ? (size_t)pl.split * M * d->cout * sizeof(float) : 0;
-}
-
-// Rows per GroupNorm-moment block of this descriptor's output as c2d_conv2d_igemm would run it, 0 =
-// the plan cannot emit moments.  One slice (after the workspace check the launch makes): the row-ring
+// Rows per GroupNorm-moment block of this descriptor's output on plan pl as the launch runs it (one slice
+// where the workspace does not hold the slabs), 0 = the plan cannot emit moments.  One slice: the row-ring
 // tiles (42: 256 rows, 43 / 44: 128) and the 256 x 320 ping-pong tile 40 (256) through their
 // workgroup-image epilogue, which needs a residual or a time embedding; K split: the combine
-// (splitk_reduce_gn_kernel, kGnRb rows) at the slice counts it is built for.  Always: no
-// quantisation-tail split, act none, 16-B outputs, groups that tile the 320-column block
+// (splitk_reduce_gn_kernel, kGnRb rows) at the slice counts it is built for.  Always: no folded upsample,
+// no quantisation-tail split, act none, 16-B outputs, groups that tile the 320-column block
 static bool gn_split_ok(int ks) {   // the slice counts splitk_reduce_gn_kernel is built for
     return ks == 2 || ks == 3 || ks == 4 || ks == 5 || ks == 6 || ks == 8 || ks == 10 || ks == 12 || ks == 15 || ks == 16;
 }
 
-static int gn_rows_for(const c2d_conv_desc* d) {
-    if (!d || d->gn_groups <= 0 || d->cout % d->gn_groups || d->up == 2 || pad_mode_check(d) != C2D_OK) return 0;
+static int gn_rows_on(const c2d_conv_desc* d, const DmaPlan& pl, bool tail_split) {
+    if (d->gn_groups <= 0 || d->cout % d->gn_groups || d->up == 2 || tail_split) return 0;
     const int cpg = d->cout / d->gn_groups;
     if (320 % cpg || d->cout % 320 || d->act != C2D_ACT_NONE) return 0;
     if ((d->out_ld & 7) || (d->resid && (d->resid_ld & 7)) || (d->temb && (d->temb_ld & 7)) || d->out_ld < d->cout) return 0;
     if (((uintptr_t)d->out | (uintptr_t)d->resid | (uintptr_t)d->temb) & 15) return 0;
-    if (d->ksize < 1 || d->oh <= 0 || d->ow <= 0 || d->n <= 0 || d->kpad < 64 || !dma_eligible(d)) return 0;
-    const long M = (long)d->n * d->oh * d->ow;
-    DmaPlan pl = plan_for(M, d->cout, d->kpad, d->act, pps_eligible(d), plan_ksize(d), rr_eligible(d), panel_eligible(d));
     if (pl.id == 50 || pl.id == 70) return 0;   // the persistent / panel tiles never split and emit none
-    bool split = false;
-    if (pl.split > 1) {
-        const size_t need = (size_t)pl.split * M * d->cout * sizeof(float);
-        split = d->ws && d->ws_bytes >= need && aligned16(d->ws);   // else the launch runs one slice
-    }
-    if (d->n >= 2 && tail_images(d, pl)) return 0;
-    if (split) {   // the split-K combine emits them (splitk_reduce_gn_kernel), kGnRb-row blocks
-        if (pl.id == 42 || pl.id == 43 || pl.id == 44) {   // the row ring's slice count (run_pp16r_t)
-            const int ncb = d->c0 / 64, cbs = (pl.nkt + 8) / 9 < 1 ? 1 : ((pl.nkt + 8) / 9 > ncb ? ncb : (pl.nkt + 8) / 9);
-            pl.split = (ncb + cbs - 1) / cbs;
-        }
+    if (pl.split > 1)   // the split-K combine emits them, kGnRb-row blocks (a row-ring plan's split is rr_slices')
         return gn_split_ok(pl.split) && ((long)d->oh * d->ow) % kGnRb == 0 ? kGnRb : 0;
-    }
     if (!(d->resid || d->temb)) return 0;   // one slice: only the workgroup-image epilogue emits them
     if (pl.id == 40) return ((long)d->oh * d->ow) % 256 == 0 ? 256 : 0;   // ping-pong 256 x 320 (igemm_pp16.h)
     if (pl.id != 42 && pl.id != 43 && pl.id != 44) return 0;
     return pl.id == 42 ? 256 : 128;
 }
 
-extern "C" int c2d_conv2d_gn_rows(const c2d_conv_desc* d) { return gn_rows_for(d); }
+// the planner's choice for d's own n * oh * ow rows
+static DmaPlan plan_of(const c2d_conv_desc* d) {
+    const long M = (long)d->n * d->oh * d->ow;
+    return plan_for(M, d->cout, d->kpad, d->act, pps_eligible(d), plan_ksize(d), rr_eligible(d), panel_eligible(d));
+}
+
+// The split-K slabs of pl, fp32 [split][n * oh * ow][cout] (0: one slice), and pl as the launch runs it: K splits
+// only into a workspace that is there, large enough and 16-B aligned, else the same tile runs one slice
+static size_t grant_slabs(const c2d_conv_desc* d, DmaPlan& pl) {
+    if (pl.split <= 1) return 0;
+    const size_t need = (size_t)pl.split * d->n * d->oh * d->ow * d->cout * sizeof(float);
+    if (!(d->ws && d->ws_bytes >= need && aligned16(d->ws))) {
+        pl.split = 1;
+        pl.nkt = d->kpad / 64;
+    }
+    return need;
+}
+
+// One descriptor resolved: what c2d_conv2d_igemm runs for it and what the three queries report, decided in
+// resolve() alone.  Read from the shape fields, which operands are set and their alignment: the queries answer
+// for descriptors without pointers; the argument and pointer checks of the launch stay in conv_run.
+enum ConvRoute { ROUTE_DMA, ROUTE_REG64, ROUTE_REG128 };   // LDS-DMA tiles / register-staged 64 x 64 / 128 x 128
+struct ConvPlan {
+    bool sized = false;     // n, oh, ow, cout > 0, ksize >= 1, kpad >= 64: a shape to plan (else the plan query
+                            // answers C2D_E_SHAPE, the others 0; the launch checks its arguments, then has no rows)
+    int rc = C2D_OK;        // fold_check / pad_mode_check: what the launch and the plan query return for the mode
+    bool refused = false;   // C2D_PRO_LNFOLD off the panel GEMM's shapes: C2D_E_SHAPE, there is no other kernel
+    ConvRoute route = ROUTE_REG64;
+    DmaPlan head = {0, 1, 0};   // ROUTE_DMA: the plan as the launch runs it (the query reports tile 0 otherwise)
+    int n1 = 0;             // quantisation tail (tail_images): images [0, n1) run head, the rest tail; 0 = one launch
+    DmaPlan tail = {0, 1, 0};
+    size_t ws_need = 0;     // split-K workspace the call asks for: the tail's slabs when it splits, else head's
+    int gn_rows = 0;        // rows per GroupNorm-moment block, 0 = this plan emits none
+};
+
+static ConvPlan resolve(const c2d_conv_desc* d) {
+    ConvPlan cp;
+    cp.sized = d->ksize >= 1 && d->oh > 0 && d->ow > 0 && d->n > 0 && d->cout > 0 && d->kpad >= 64;
+    if (d->up == 2) cp.rc = fold_check(d);   // folded upsample: everything it does not take is refused
+    if (cp.rc == C2D_OK) cp.rc = pad_mode_check(d);
+    cp.refused = d->pro == C2D_PRO_LNFOLD && !panel_eligible(d);
+    if (!cp.sized || cp.rc != C2D_OK) return cp;
+    if (!dma_eligible(d)) {
+        const long M = (long)d->n * d->oh * d->ow;
+        cp.route = ((M + 127) / 128) * ((d->cout + 127) / 128) < 512 ? ROUTE_REG64 : ROUTE_REG128;
+        return cp;
+    }
+    cp.route = ROUTE_DMA;
+    cp.head = plan_of(d);
+    // only the panel GEMM folds a LayerNorm.  (A refused descriptor keeps the planner's tile for the moments
+    // query, which has always answered without this rule: DESIGN.md, planner findings)
+    if (d->pro == C2D_PRO_LNFOLD && !cp.refused) cp.head = {70, 1, d->kpad / 64};
+    cp.n1 = tail_images(d, cp.head);
+    if (cp.n1) {   // the head runs one slice; the workspace is the tail's
+        const c2d_conv_desc t = tail_desc(d, cp.n1);
+        cp.tail = plan_of(&t);
+        cp.ws_need = grant_slabs(&t, cp.tail);
+    } else {
+        cp.ws_need = grant_slabs(d, cp.head);
+    }
+    cp.gn_rows = gn_rows_on(d, cp.head, cp.n1 != 0);
+    return cp;
+}
+
+extern "C" size_t c2d_conv2d_igemm_workspace_size(const c2d_conv_desc* d) {
+    if (!d) return 0;
+    const ConvPlan cp = resolve(d);
+    return cp.refused ? 0 : cp.ws_need;
+}
+
+extern "C" int c2d_conv2d_gn_rows(const c2d_conv_desc* d) { return d ? resolve(d).gn_rows : 0; }
 
 extern "C" int c2d_conv2d_igemm_plan(const c2d_conv_desc* d, int* tile_id, int* ksplit) {
     if (!d || !tile_id || !ksplit) return C2D_E_ARG;
-    if (d->ksize < 1 || d->oh <= 0 || d->ow <= 0 || d->n <= 0 || d->cout <= 0 || d->kpad < 64) return C2D_E_SHAPE;
-    if (d->up == 2) {   // folded upsample: as the launch validates it
-        const int rc = fold_check(d);
-        if (rc != C2D_OK) return rc;
-    }
-    if (const int rc = pad_mode_check(d)) return rc;
-    if (d->pro == C2D_PRO_LNFOLD) {   // the panel GEMM or nothing (c2d_conv2d_igemm rejects the rest the same way)
-        if (!panel_eligible(d)) return C2D_E_SHAPE;
-        *tile_id = 70;
-        *ksplit = 1;
-        return C2D_OK;
-    }
-    if (!dma_eligible(d)) {
-        *tile_id = 0;
-        *ksplit = 1;
-        return C2D_OK;
-    }
-    const long M = (long)d->n * d->oh * d->ow;
-    DmaPlan pl = plan_for(M, d->cout, d->kpad, d->act, pps_eligible(d), plan_ksize(d), rr_eligible(d), panel_eligible(d));
-    if (pl.split > 1) {
-        const size_t need = (size_t)pl.split * M * d->cout * sizeof(float);
-        if (!(d->ws && d->ws_bytes >= need && aligned16(d->ws))) pl.split = 1;
-    }
-    *tile_id = pl.id;
-    *ksplit = pl.split;
+    const ConvPlan cp = resolve(d);
+    if (!cp.sized) return C2D_E_SHAPE;
+    if (cp.rc != C2D_OK) return cp.rc;
+    if (cp.refused) return C2D_E_SHAPE;
+    *tile_id = cp.head.id;
+    *ksplit = cp.head.split;
     return C2D_OK;
 }
 
-static int conv_run(const c2d_conv_desc* d, hipStream_t s, const DmaPlan* fixed);
+static int conv_run(const c2d_conv_desc* d, hipStream_t s, const ConvPlan& cp, const DmaPlan& pl);
 
 extern "C" int c2d_conv2d_igemm(const c2d_conv_desc* d, void* stream) {
     if (!d || !d->src0 || !d->weight || !d->out) return C2D_E_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (d->up < 0 || d->up > 2) return C2D_E_ARG;
-    if (d->up == 2) {   // folded upsample: everything it does not take is refused here, nothing launched
-        const int rc = fold_check(d);
-        if (rc != C2D_OK) return rc;
-    }
-    if (const int rc = pad_mode_check(d)) return rc;
-    if (d->gn_mom && gn_rows_for(d) == 0) return C2D_E_SHAPE;   // moments requested of a plan that cannot emit them
+    const ConvPlan cp = resolve(d);
+    if (cp.rc != C2D_OK) return cp.rc;   // nothing launched
+    if (d->gn_mom && cp.gn_rows == 0) return C2D_E_SHAPE;   // moments requested of a plan that cannot emit them
     if (d->gn_mom && ((uintptr_t)d->gn_mom & 7)) return C2D_E_ALIGN;
-    if (d->n >= 2 && d->ksize >= 1 && d->oh > 0 && d->ow > 0 && d->cout > 0 && d->kpad >= 64 && dma_eligible(d)) {
-        const long M = (long)d->n * d->oh * d->ow;
-        const DmaPlan pl = plan_for(M, d->cout, d->kpad, d->act, pps_eligible(d), plan_ksize(d), rr_eligible(d), panel_eligible(d));
-        if (const int n1 = tail_images(d, pl)) {   // quantisation tail: whole rounds, then the rest
-            c2d_conv_desc head = *d;
-            head.n = n1;
-            const int rc = conv_run(&head, s, &pl);
-            if (rc != C2D_OK) return rc;
-            const c2d_conv_desc tail = tail_desc(d, n1);
-            return conv_run(&tail, s, nullptr);
-        }
-    }
-    return conv_run(d, s, nullptr);
+    if (!cp.n1) return conv_run(d, s, cp, cp.head);
+    c2d_conv_desc head = *d;   // quantisation tail: whole rounds, then the rest
+    head.n = cp.n1;
+    const int rc = conv_run(&head, s, cp, cp.head);
+    if (rc != C2D_OK) return rc;
+    const c2d_conv_desc tail = tail_desc(d, cp.n1);
+    return conv_run(&tail, s, cp, cp.tail);
 }
 
-// fixed: run this plan (the head of a tail split) instead of planning for d's own M
-static int conv_run(const c2d_conv_desc* d, hipStream_t s, const DmaPlan* fixed) {
-    if (!d || !d->src0 || !d->weight || !d->out) return C2D_E_ARG;
+// one launch of the resolved plan: d is the call's descriptor, or its head / tail images with their plan pl
+static int conv_run(const c2d_conv_desc* d, hipStream_t s, const ConvPlan& cp, const DmaPlan& pl) {
     if (d->ksize != 1 && d->ksize != 3) return C2D_E_SHAPE;
     if (d->c1 > 0 && !d->src1) return C2D_E_ARG;
     const int cin = d->c0 + d->c1;
     if ((d->c0 & 7) || (d->c1 & 7) || cin <= 0) return C2D_E_SHAPE;
     if (d->kpad & 63) return C2D_E_SHAPE;
-    const bool fold = d->up == 2;   // validated by c2d_conv2d_igemm (fold_check)
+    const bool fold = d->up == 2;   // validated by resolve (fold_check)
     const int ktot = (fold ? 4 : d->ksize * d->ksize) * cin;
     if (d->kpad < ktot) return C2D_E_SHAPE;
     if ((d->cout & 3) || d->cout <= 0) return C2D_E_SHAPE;
@@ -1642,7 +1659,7 @@ static int conv_run(const c2d_conv_desc* d, hipStream_t s, const DmaPlan* fixed)
     if (d->pro == C2D_PRO_LN && (!d->pro_a || !d->gamma || !d->beta)) return C2D_E_ARG;
     if (d->pro < 0 || d->pro > 4 || d->act < 0 || d->act > 5) return C2D_E_ARG;
     if (d->pro == C2D_PRO_LNFOLD && !(d->pro_eps > 0.f)) return C2D_E_ARG;   // pro_eps: read only for LNFOLD
-    if (d->pro == C2D_PRO_LNFOLD && !panel_eligible(d)) return C2D_E_SHAPE;   // only the panel GEMM folds LN
+    if (cp.refused) return C2D_E_SHAPE;
     if (d->stride != 1 && d->stride != 2) return C2D_E_SHAPE;
     if (d->ksize == 1 && (d->stride != 1 || d->up || d->oh != d->h || d->ow != d->w)) return C2D_E_SHAPE;
     if (d->up && d->stride != 1) return C2D_E_SHAPE;
@@ -1679,37 +1696,21 @@ static int conv_run(const c2d_conv_desc* d, hipStream_t s, const DmaPlan* fixed)
         p.oh = d->h; p.ow = d->w;
         p.M = d->n * d->h * d->w;
     }
-    const long M_all = (long)d->n * d->oh * d->ow;   // output rows (fold: 4 p.M)
-    p.gn_mom = (float*)d->gn_mom;   // c2d_conv2d_igemm checked gn_rows_for: a one-slice row-ring plan
+    p.gn_mom = (float*)d->gn_mom;   // c2d_conv2d_igemm checked ConvPlan::gn_rows: this plan emits them
     p.gn_cpg = d->gn_mom ? d->cout / d->gn_groups : 0;
     if (p.M <= 0) return C2D_OK;
 
     const int amode = (d->ksize == 1) ? AM_1X1 : ((cin % 64) == 0 ? AM_3X3_FAST : AM_3X3_GEN);
-    const bool dma = dma_eligible(d);
     p.ksplit = 1;
     p.nkt = d->kpad / 64;
-    p.ws = nullptr;
+    p.ws = pl.split > 1 ? (float*)d->ws : nullptr;   // resolve granted the split against this workspace
     p.slab16 = tuning().splitk_f16;
     p.abl = gemm_abl();
     p.lds_epi = (gemm_lds_epi() || !epi_direct_ok(d)) ? 1 : 0;
     p.cmajor = gemm_korder();
-    const long t128 = (long)((p.M + 127) / 128) * ((d->cout + 127) / 128);
-    if (dma) {
-        DmaPlan pl = fixed ? *fixed : plan_for(M_all, d->cout, d->kpad, d->act, pps_eligible(d), plan_ksize(d), rr_eligible(d), panel_eligible(d));
-        if (d->pro == C2D_PRO_LNFOLD) pl = {70, 1, d->kpad / 64};   // validated above: panel_eligible
-        if (pl.split > 1) {
-            const size_t need = (size_t)pl.split * M_all * d->cout * sizeof(float);
-            if (d->ws && d->ws_bytes >= need && aligned16(d->ws)) {
-                p.ws = (float*)d->ws;
-            } else {  // no / short workspace: same tile, one K slice
-                pl.split = 1;
-                pl.nkt = d->kpad / 64;
-            }
-        }
+    if (cp.route == ROUTE_DMA) {
         dispatch_dma(p, pl, plan_ksize(d), d->cout, s);
-    } else if (fold) {
-        return C2D_E_SHAPE;
-    } else if (t128 < 512) {
+    } else if (cp.route == ROUTE_REG64) {
         p.gx = (d->cout + 63) / 64; p.gy = (p.M + 63) / 64;
         if (amode == AM_1X1) launch<64, 64, AM_1X1>(p, s);
         else if (amode == AM_3X3_FAST) launch<64, 64, AM_3X3_FAST>(p, s);

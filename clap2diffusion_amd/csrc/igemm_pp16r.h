@@ -413,12 +413,9 @@ static void run_pp16r_t(IgemmParams& p, hipStream_t s) {
     p.gx = (p.cout + BN - 1) / BN;
     p.gy = p.M / BM;
     // K steps per slice: whole channel blocks (9 steps each)
-    const int ncb = p.cin / 64;
-    int cbs = (p.nkt + 8) / 9;
-    if (cbs < 1) cbs = 1;
-    if (cbs > ncb) cbs = ncb;
-    p.ksplit = (ncb + cbs - 1) / cbs;
-    p.nkt = 9 * cbs;
+    const RrSlices rs = rr_slices(p.cin / 64, p.nkt);
+    p.ksplit = rs.split;
+    p.nkt = rs.nkt;
     ensure_lds<igemm_pp16r_kernel<TN, PH, W, TMW, NB, NRG>>(smem);
     hipLaunchKernelGGL((igemm_pp16r_kernel<TN, PH, W, TMW, NB, NRG>), dim3(p.gx * p.gy * p.ksplit), dim3(512), smem, s, p);
     if (p.ksplit > 1) run_splitk_reduce(p, s);

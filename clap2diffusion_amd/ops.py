@@ -11,11 +11,12 @@ from __future__ import annotations
 import ctypes
 import functools
 import math
+import os
 
 import torch
 
 from . import torch_ops  # noqa: F401  (registers the c2d:: operators)
-from ._lib import C2D_ACT
+from ._lib import C2D_ACT, C2D_PRO_LNFOLD, ConvDesc, check, lib
 
 C2D = torch.ops.c2d
 
@@ -93,17 +94,44 @@ def fold_upsample_weight(w: torch.Tensor, dtype: torch.dtype = F16) -> tuple[tor
     return out.reshape(4, cout, 4 * cin).to(dtype).contiguous(), 4 * cin
 
 
+def _shape_desc(n: int, h: int, w: int, c0: int, cout: int, ksize: int, *, c1: int = 0, oh: int | None = None,
+                ow: int | None = None, stride: int = 1, up: int = 0, kpad: int | None = None, act: str | None = None,
+                out_ld: int | None = None, src_pad: bool = False, lnfold: bool = False, resid: bool = False,
+                temb: bool = False, groups: int = 0, operands: bool = False) -> ConvDesc:
+    """A c2d_conv_desc of shapes and flags for the planner's queries, which read no memory: output oh x ow (h x w
+    unless given), kpad of the plain K = ksize^2 (c0 + c1), out_ld = cout.  resid / temb: a 16-B aligned stand-in of
+    leading dimension cout; operands: the same for out and src1, and a workspace that holds any split, as ops.conv
+    passes them (the queries only test pointers for presence and alignment)."""
+    d = ConvDesc()
+    d.c0, d.c1, d.n, d.h, d.w, d.oh, d.ow = c0, c1, n, h, w, (h if oh is None else oh), (w if ow is None else ow)
+    d.ksize, d.stride, d.up, d.src_pad, d.act = ksize, stride, up, int(src_pad), C2D_ACT[act]
+    d.cout, d.kpad = cout, (kpad_of(ksize * ksize * (c0 + c1)) if kpad is None else kpad)
+    d.out_ld, d.gn_groups = (cout if out_ld is None else out_ld), groups
+    if lnfold:
+        d.pro, d.pro_eps = C2D_PRO_LNFOLD, 1e-5
+    if resid:
+        d.resid, d.resid_ld = 256, cout
+    if temb:
+        d.temb, d.temb_ld = 256, cout
+    if operands:
+        d.out, d.ws, d.ws_bytes = 256, 256, 1 << 40
+        if c1:
+            d.src1 = 256
+    return d
+
+
+def _plan_query(d: ConvDesc) -> tuple[int, int, int]:
+    """c2d_conv2d_igemm_plan -> (return code, tile id, K slices)."""
+    tid, ks = ctypes.c_int(), ctypes.c_int()
+    rc = lib().c2d_conv2d_igemm_plan(ctypes.byref(d), ctypes.byref(tid), ctypes.byref(ks))
+    return rc, tid.value, ks.value
+
+
 @functools.lru_cache(maxsize=None)
 def upfold_ok(n: int, h: int, w: int, cin: int, cout: int) -> bool:
     """Does the library take this Upsample2D conv as a folded upsample (c2d_conv_desc::up = 2)?  Not with
     cin % 64 != 0, nor a build without the mode: the caller then materialises the x2 tensor."""
-    import ctypes
-    from ._lib import ConvDesc, lib
-    d = ConvDesc()
-    d.c0, d.n, d.h, d.w, d.oh, d.ow, d.ksize, d.stride, d.up = cin, n, h, w, 2 * h, 2 * w, 3, 1, 2
-    d.cout, d.kpad, d.out_ld = cout, 4 * cin, cout
-    tid, ks = ctypes.c_int(), ctypes.c_int()
-    return lib().c2d_conv2d_igemm_plan(ctypes.byref(d), ctypes.byref(tid), ctypes.byref(ks)) == 0
+    return _plan_query(_shape_desc(n, h, w, cin, cout, 3, oh=2 * h, ow=2 * w, up=2, kpad=4 * cin))[0] == 0
 
 
 def geglu_interleave(w: torch.Tensor, b: torch.Tensor | None):
@@ -158,11 +186,7 @@ def conv(x: torch.Tensor, weight: torch.Tensor, kpad: int, cout: int, *, ksize: 
     if pad_after:
         assert ksize == 3 and stride == 2 and not up and not up_fold and not padded and x.dim() == 4
         assert h % 2 == 0 and w % 2 == 0, "pad-after downsample: even H and W"
-    if ksize == 3:
-        vh, vw = (2 * h, 2 * w) if up or up_fold else (h, w)
-        oh, ow = (vh + 2 - 3) // stride + 1, (vw + 2 - 3) // stride + 1
-    else:
-        oh, ow = h, w
+    oh, ow = torch_ops.conv_out_hw(h, w, ksize, stride, up, up_fold, pad_after)
     out_cols = cout // 2 if act == "geglu" else cout
     if out is None:
         shape = (x.shape[0], out_cols) if x.dim() == 2 else (x.shape[0], oh, ow, out_cols)
@@ -203,22 +227,9 @@ def gn_moment_rows(n: int, oh: int, ow: int, cin: int, cout: int, ksize: int, st
                    temb: bool, groups: int, c1: int = 0) -> int:
     """c2d_conv2d_gn_rows for a conv of these shapes as ops.conv issues it (16-B aligned operands, a workspace
     for any split): rows per moment block, 0 = this conv cannot emit its output's GroupNorm moments."""
-    import ctypes
-    from ._lib import ConvDesc, lib
-    d = ConvDesc()
     h, w = (oh, ow) if padded or ksize == 1 or stride == 1 else (oh * stride, ow * stride)
-    d.c0, d.n, d.h, d.w, d.oh, d.ow, d.ksize, d.stride, d.src_pad = cin, n, h, w, oh, ow, ksize, stride, int(padded)
-    d.c1 = c1
-    if c1:
-        d.src1 = 256
-    d.cout, d.kpad, d.out_ld = cout, kpad_of(ksize * ksize * (cin + c1)), cout
-    d.out = 256
-    if resid:
-        d.resid, d.resid_ld = 256, cout
-    if temb:
-        d.temb, d.temb_ld = 256, cout
-    d.ws, d.ws_bytes = 256, 1 << 40
-    d.gn_groups = groups
+    d = _shape_desc(n, h, w, cin, cout, ksize, c1=c1, oh=oh, ow=ow, stride=stride, src_pad=padded, resid=resid,
+                    temb=temb, groups=groups, operands=True)
     return int(lib().c2d_conv2d_gn_rows(ctypes.byref(d)))
 
 
@@ -241,17 +252,9 @@ def panel_gemm(m: int, k: int, cout: int, geglu: bool, lnfold: bool = False) -> 
     """Does c2d's planner run this 1x1 GEMM (m x k -> cout) on the panel GEMM (tile 70)?  Where it
     does, a LayerNorm before it folds in.  lnfold: would the library take this GEMM with a folded
     LayerNorm (C2D_PRO_LNFOLD: the panel GEMM's shapes and switches, else C2D_E_SHAPE)?"""
-    import ctypes
-    from ._lib import C2D_PRO_LNFOLD, ConvDesc, lib
-    d = ConvDesc()
-    d.c0, d.n, d.h, d.w, d.oh, d.ow, d.ksize, d.stride = k, 1, 1, m, 1, m, 1, 1
-    d.cout, d.kpad, d.act = cout, kpad_of(k), C2D_ACT["geglu" if geglu else None]
-    d.out_ld = cout // 2 if geglu else cout
-    if lnfold:
-        d.pro, d.pro_eps = C2D_PRO_LNFOLD, 1e-5
-    tid, ks = ctypes.c_int(), ctypes.c_int()
-    rc = lib().c2d_conv2d_igemm_plan(ctypes.byref(d), ctypes.byref(tid), ctypes.byref(ks))
-    return rc == 0 and tid.value == 70
+    rc, tile, _ = _plan_query(_shape_desc(1, 1, m, k, cout, 1, act="geglu" if geglu else None,
+                                          out_ld=cout // 2 if geglu else cout, lnfold=lnfold))
+    return rc == 0 and tile == 70
 
 
 ROWRING_TILES = (42, 43, 44)   # igemm_pp16r.h: output width 64 / 32 / 16
@@ -262,39 +265,29 @@ def rowring_conv(n: int, h: int, w: int, cin: int, cout: int) -> bool:
     """Does c2d's planner run a 3x3 stride-1 conv (n x h x w, cin -> cout) on a row-ring tile (42 / 43
     / 44, by output width) when its source is zero-bordered?  (Asked of the library, c2d_conv2d_igemm_plan: the padded
     layout is worth writing only where that kernel reads it.)"""
-    import ctypes
-    from ._lib import ConvDesc, check, lib
-    d = ConvDesc()
-    d.c0, d.n, d.h, d.w, d.oh, d.ow, d.ksize, d.stride = cin, n, h, w, h, w, 3, 1
-    d.cout, d.kpad, d.src_pad = cout, kpad_of(9 * cin), 1
-    d.out_ld = cout
-    tid, ks = ctypes.c_int(), ctypes.c_int()
-    check(lib().c2d_conv2d_igemm_plan(ctypes.byref(d), ctypes.byref(tid), ctypes.byref(ks)), "c2d_conv2d_igemm_plan")
-    return tid.value in ROWRING_TILES
+    rc, tile, _ = _plan_query(_shape_desc(n, h, w, cin, cout, 3, src_pad=True))
+    check(rc, "c2d_conv2d_igemm_plan")
+    return tile in ROWRING_TILES
 
 
 def conv_workspace_bytes(n: int, h: int, w: int, c0: int, c1: int, cout: int, ksize: int) -> int:
     """Split-K workspace c2d_conv2d_igemm asks for on a stride-1 conv (n x h x w, c0 [+ c1] -> cout),
     as torch_ops.conv2d_igemm allocates it (c2d_conv2d_igemm_workspace_size)."""
-    import ctypes
-    from ._lib import ConvDesc, lib
-    d = ConvDesc()
-    d.c0, d.c1, d.n, d.h, d.w, d.oh, d.ow, d.ksize, d.stride = c0, c1, n, h, w, h, w, ksize, 1
-    d.cout, d.kpad, d.out_ld = cout, kpad_of(ksize * ksize * (c0 + c1)), cout
-    return int(lib().c2d_conv2d_igemm_workspace_size(ctypes.byref(d)))
+    return int(lib().c2d_conv2d_igemm_workspace_size(ctypes.byref(_shape_desc(n, h, w, c0, cout, ksize, c1=c1))))
 
 
 class record_conv_plans:
     """Context manager collecting the (tile_id, ksplit) plan of every conv call
-    (c2d_conv2d_igemm_plan) -- lets tests assert which kernel configuration ran."""
+    (c2d_conv2d_igemm_plan) -- lets tests assert which kernel configuration ran -- and, in ws_bytes, the
+    split-K workspace each call allocated."""
 
     def __enter__(self):
-        self.plans = []
-        torch_ops._plan_probe = self.plans
+        self.plans, self.ws_bytes = [], []
+        torch_ops._plan_probe, torch_ops._ws_probe = self.plans, self.ws_bytes
         return self.plans
 
     def __exit__(self, *exc):
-        torch_ops._plan_probe = None
+        torch_ops._plan_probe = torch_ops._ws_probe = None
         return False
 
 
@@ -306,8 +299,6 @@ class force_plan:
         self.tile, self.split = int(tile), int(split)
 
     def __enter__(self):
-        import ctypes
-        from ._lib import check, lib
         t, sp = ctypes.c_int(0), ctypes.c_int(0)
         check(lib().c2d_get_plan_override(ctypes.byref(t), ctypes.byref(sp)), "c2d_get_plan_override")
         self.prev = (t.value, sp.value)   # restored on exit: nested overrides / env sweeps survive
@@ -317,7 +308,6 @@ class force_plan:
         return self
 
     def __exit__(self, *exc):
-        from ._lib import lib
         lib().c2d_set_plan_override(*self.prev)
         rowring_conv.cache_clear()
         gn_moment_rows.cache_clear()
@@ -327,8 +317,6 @@ class force_plan:
 def plan_override_from_env() -> None:
     """Opt-in for the tuning scripts: C2D_GEMM_TILE / C2D_GEMM_SPLIT (environment) ->
     c2d_set_plan_override.  The library itself never reads them."""
-    import os
-    from ._lib import check, lib
     t, sp = int(os.environ.get("C2D_GEMM_TILE", "0") or 0), int(os.environ.get("C2D_GEMM_SPLIT", "0") or 0)
     if t or sp:
         check(lib().c2d_set_plan_override(t, sp), "c2d_set_plan_override")

@@ -23,6 +23,17 @@ from ._lib import C2D_PAD_AFTER, C2D_PAD_SAME, C2D_PRO_GN, C2D_PRO_LN, C2D_PRO_L
 _CU = "cuda"
 
 
+def conv_out_hw(h: int, w: int, ksize: int, stride: int, up: bool, up_fold: bool, pad_after: bool) -> tuple[int, int]:
+    """Output size of c2d::conv2d_igemm over an h x w image: a 3x3 pads 1 on the (nearest-x2, up or up_fold) view;
+    pad_after is F.pad(x, (0, 1, 0, 1)) + conv(stride 2, padding 0), (h + 1 - 3) // 2 + 1; a 1x1 keeps the size."""
+    if ksize != 3:
+        return h, w
+    if pad_after:
+        return (h - 2) // 2 + 1, (w - 2) // 2 + 1
+    vh, vw = (2 * h, 2 * w) if up or up_fold else (h, w)
+    return (vh + 2 - 3) // stride + 1, (vw + 2 - 3) // stride + 1
+
+
 def _conv_desc(x, weight, kpad, cout, ksize, stride, up, x2, gn_scale, gn_shift, gn_silu, ln_stats, ln_gamma,
                ln_beta, silu_in, bias, act, temb, resid, out, src_pad=False, lnf_eps=0.0, gn_mom=None,
                gn_groups=0, up_fold=False, pad_after=False) -> ConvDesc:
@@ -34,13 +45,7 @@ def _conv_desc(x, weight, kpad, cout, ksize, stride, up, x2, gn_scale, gn_shift,
         if src_pad:   # zero-bordered [n][h + 2][w + 2][c0]: logical size h x w
             h, w = h - 2, w - 2
     c1 = x2.shape[-1] if x2 is not None else 0
-    if ksize == 3:
-        vh, vw = (2 * h, 2 * w) if up or up_fold else (h, w)
-        oh, ow = (vh + 2 - 3) // stride + 1, (vw + 2 - 3) // stride + 1
-        if pad_after:   # F.pad(x, (0, 1, 0, 1)) + conv(stride 2, padding 0): (h + 1 - 3) // 2 + 1
-            oh, ow = (h - 2) // 2 + 1, (w - 2) // 2 + 1
-    else:
-        oh, ow = h, w
+    oh, ow = conv_out_hw(h, w, ksize, stride, up, up_fold, pad_after)
     d = ConvDesc()
     d.src0 = ptr(x); d.src1 = ptr(x2); d.c0 = c0; d.c1 = c1
     d.n, d.h, d.w, d.oh, d.ow = n, h, w, oh, ow
@@ -71,7 +76,8 @@ def _conv_desc(x, weight, kpad, cout, ksize, stride, up, x2, gn_scale, gn_shift,
     return d
 
 
-_plan_probe: Optional[list] = None
+_plan_probe: Optional[list] = None   # ops.record_conv_plans: the (tile, K slices) c2d_conv2d_igemm_plan reports per call
+_ws_probe: Optional[list] = None     # ... and the bytes of split-K workspace the call allocated
 
 
 @custom_op("c2d::conv2d_igemm", mutates_args=("out",), device_types=_CU)
@@ -97,6 +103,8 @@ def conv2d_igemm(x: Tensor, weight: Tensor, kpad: int, cout: int, ksize: int, st
     if wsb:
         ws = torch.empty(wsb // 4, device=x.device, dtype=torch.float32)
         d.ws = ptr(ws); d.ws_bytes = wsb
+    if _ws_probe is not None:
+        _ws_probe.append(ws.numel() * ws.element_size() if wsb else 0)
     if _plan_probe is not None:
         tid, ks = ctypes.c_int(), ctypes.c_int()
         check(lib().c2d_conv2d_igemm_plan(ctypes.byref(d), ctypes.byref(tid), ctypes.byref(ks)), "c2d_conv2d_igemm_plan")

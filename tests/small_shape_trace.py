@@ -9,11 +9,15 @@ launches(h, w)        the set of launch keys at latent h x w (UNet at the CFG pa
 never_made()          launches(8, 8) - launches(16, 16): what the suite's smallest latent never launched
 plan_rows(keys)       for every conv / linear key: a filled c2d_conv_desc asked of c2d_conv2d_igemm_plan,
                       c2d_conv2d_igemm_workspace_size and c2d_conv2d_gn_rows
+plan_table()          the planner's answers over the runs of PLAN_TABLE_RUNS and the towers' linear shapes, with the
+                      launch-key digest of every run (tests/golden/conv_plan_table.json)
 CPU only: nothing here touches a device.
 """
 from __future__ import annotations
 
 import ctypes
+import functools
+import hashlib
 
 import torch
 from torch._subclasses.fake_tensor import FakeTensorMode
@@ -69,15 +73,18 @@ def unet_calls(h: int, w: int, n: int = 2):
     return _run(go)
 
 
-def vae_calls(h: int, w: int, n: int = 1):
+def vae_calls(h: int, w: int, n: int = 1, parts=("dec", "enc")):
     from clap2diffusion_amd.vae import VAEDecoder, VAEEncoder
 
     def go():
-        dec, enc = VAEDecoder(), VAEEncoder()
-        dec.decoder.mid_block.attentions[0].finalize()
-        enc.encoder.mid_block.attentions[0].finalize()
-        dec(torch.empty(n, 4, h, w, dtype=torch.float32))
-        enc(torch.empty(n, 8 * h, 8 * w, 3, dtype=torch.uint8))
+        if "dec" in parts:
+            dec = VAEDecoder()
+            dec.decoder.mid_block.attentions[0].finalize()
+            dec(torch.empty(n, 4, h, w, dtype=torch.float32))
+        if "enc" in parts:
+            enc = VAEEncoder()
+            enc.encoder.mid_block.attentions[0].finalize()
+            enc(torch.empty(n, 8 * h, 8 * w, 3, dtype=torch.uint8))
     return _run(go)
 
 
@@ -177,3 +184,138 @@ def summary(keys) -> dict:
         sig = [[k, list(v[1]), v[2]] if isinstance(v, tuple) else [k, v] for k, v in items]
         out.setdefault(op, []).append(sig)
     return {k: sorted(v, key=repr) for k, v in sorted(out.items())}
+
+
+# ------------------------------------------------------------------ the plan table
+# (name, calls): the runs whose conv / linear launches make the rows of tests/golden/conv_plan_table.json
+PLAN_TABLE_RUNS = (
+    ("unet_8x8_n2", lambda: unet_calls(8, 8, 2)),
+    ("unet_16x16_n2", lambda: unet_calls(16, 16, 2)),
+    ("unet_64x64_n2", lambda: unet_calls(64, 64, 2)),
+    ("unet_64x64_n32", lambda: unet_calls(64, 64, 32)),
+    ("unet_96x96_n16", lambda: unet_calls(96, 96, 16)),
+    ("vae_8x8_n1", lambda: vae_calls(8, 8, 1)),
+    ("vae_64x64_n1", lambda: vae_calls(64, 64, 1)),
+    ("vae_dec_64x64_n8", lambda: vae_calls(64, 64, 8, parts=("dec",))),
+)
+DESC_FIELDS = ("n", "h", "w", "c0", "c1", "oh", "ow", "ksize", "stride", "up", "cout", "kpad", "pro", "act", "bias",
+               "temb_ld", "resid_ld", "out_ld", "src_pad", "pad_mode")
+# per variant: (rc, tile, split) of c2d_conv2d_igemm_plan without a workspace, with a large one and with one a byte
+# short of the need; c2d_conv2d_igemm_workspace_size; c2d_conv2d_gn_rows at 32 groups with and without a residual
+ANSWER_FIELDS = ("rc0", "tile0", "split0", "rc", "tile", "split", "rc_short", "tile_short", "split_short", "ws_bytes",
+                 "gn_rows_resid", "gn_rows_plain")
+
+
+def tower_linears() -> list:
+    """(M, K, cout) of every HLinear of the CLIP text tower (one prompt and the CFG pair), the CLIP vision tower
+    (one image, with and without the class row) and HTSAT (one clip), from the modules' own sizes."""
+    from clap2diffusion_amd.htsat import HTSATEncoder
+    from clap2diffusion_amd.layers import HLinear
+    from clap2diffusion_amd.weights import CLIP_VISION_CFG as V
+    out = []
+    for m in (154, 77):   # text_encoder.TextEncoder: 77 tokens of width 768, mlp 3072
+        out += [(m, 768, 2304), (m, 768, 768), (m, 768, 3072), (m, 3072, 768)]
+    w, tokens = V["width"], (V["image"] // V["patch"]) ** 2
+    out.append((tokens, 3 * V["patch"] ** 2, w))   # patch_embed: K = 588 -> kpad 640
+    for m in (tokens + 1, tokens):
+        out += [(m, w, 3 * w), (m, w, w), (m, w, V["mlp"]), (m, V["mlp"], w)]
+    out.append((1, w, V["proj"]))
+    with torch.device("meta"):
+        enc = HTSATEncoder()
+    rows = 4096   # 64 x 64 patches of a 1024-frame clip, a quarter after every merge
+    out.append((rows, enc.patch_proj.in_features, enc.patch_proj.out_features))
+    for i, stage in enumerate(enc.stages):
+        for lin in (x for x in stage.modules() if isinstance(x, HLinear)):
+            out.append((rows, lin.in_features, lin.out_features))
+        if i < len(enc.merges):
+            rows //= 4
+            out.append((rows, enc.merges[i].reduction.in_features, enc.merges[i].reduction.out_features))
+    out += [(1, enc.linear1.in_features, enc.linear1.out_features), (1, enc.linear2.in_features, enc.linear2.out_features)]
+    return sorted(set(out))
+
+
+def linear_desc(m: int, k: int, cout: int):
+    """A plain linear (no prologue, activation, residual) of m rows as ops.conv issues it for a 2-D input."""
+    from clap2diffusion_amd import _lib
+    d = _lib.ConvDesc()
+    d.src0, d.weight, d.bias, d.out = 256, 256, 256, 256
+    d.c0, d.n, d.h, d.w, d.oh, d.ow, d.ksize, d.stride = k, 1, 1, m, 1, m, 1, 1
+    d.cout, d.kpad, d.out_ld = cout, (k + 63) // 64 * 64, cout
+    return d
+
+
+def answers(d) -> list:
+    """ANSWER_FIELDS for descriptor d under the plan override in force; d comes back as it was."""
+    from clap2diffusion_amd import _lib
+    L = _lib.lib()
+    keep = (d.ws, d.ws_bytes, d.resid, d.resid_ld, d.gn_groups)
+    d.ws, d.ws_bytes = None, 0
+    need = int(L.c2d_conv2d_igemm_workspace_size(ctypes.byref(d)))
+    out = []
+    for ws, nbytes in ((None, 0), (256, 1 << 40), (256, max(need - 1, 0))):
+        d.ws, d.ws_bytes = ws, nbytes
+        tid, ks = ctypes.c_int(-9), ctypes.c_int(-9)
+        out += [L.c2d_conv2d_igemm_plan(ctypes.byref(d), ctypes.byref(tid), ctypes.byref(ks)), tid.value, ks.value]
+    out.append(need)
+    d.ws, d.ws_bytes, d.gn_groups = 256, 1 << 40, 32
+    for resid in (True, False):
+        d.resid, d.resid_ld = (256, keep[3] or d.cout) if resid else (None, 0)
+        out.append(int(L.c2d_conv2d_gn_rows(ctypes.byref(d))) if d.cout % 32 == 0 else 0)
+    d.ws, d.ws_bytes, d.resid, d.resid_ld, d.gn_groups = keep
+    return out
+
+
+def launch_digest(calls) -> str:
+    return hashlib.sha256(repr(sorted(set(calls), key=repr)).encode()).hexdigest()[:16]
+
+
+@functools.lru_cache(maxsize=None)
+def plan_table() -> dict:
+    """{"runs": {name: {"launches": distinct launch keys, "digest": their hash}}, "rows": [...]}: one row per distinct
+    descriptor of the runs' conv / linear launches and of tower_linears(), "d" its DESC_FIELDS, "base" its
+    ANSWER_FIELDS; the 3x3 rows with c0 + c1 a multiple of 64 also "src_pad" (the answers with src_pad = 1) and
+    "forced" ({"tile/split": answers} under ops.force_plan for every LDS-DMA tile and the panel GEMM, split 0 and
+    2)."""
+    from clap2diffusion_amd import ops
+    from tests.test_kernels_gpu import DMA_TILE_IDS
+    runs, descs = {}, {}
+    for name, calls in PLAN_TABLE_RUNS:
+        keys = set(calls())
+        runs[name] = {"launches": len(keys), "digest": launch_digest(keys)}
+        for key in keys:
+            if key[0] == "conv2d_igemm":
+                d = conv_desc_of(key)
+                row = tuple(int(bool(getattr(d, f))) if f == "bias" else getattr(d, f) for f in DESC_FIELDS)
+                descs.setdefault(row, d)
+    for shape in tower_linears():
+        d = linear_desc(*shape)
+        descs.setdefault(tuple(int(bool(getattr(d, f))) if f == "bias" else getattr(d, f) for f in DESC_FIELDS), d)
+    rows = []
+    for key in sorted(descs):
+        d = descs[key]
+        row = {"d": list(key), "base": answers(d)}
+        if d.ksize == 3 and (d.c0 + d.c1) % 64 == 0:
+            if not d.src_pad:
+                d.src_pad = 1
+                row["src_pad"] = answers(d)
+                d.src_pad = 0
+            row["forced"] = {}
+            for tile in (*DMA_TILE_IDS, 70):
+                for split in (0, 2):
+                    with ops.force_plan(tile, split):
+                        row["forced"][f"{tile}/{split}"] = answers(d)
+        rows.append(row)
+    return {"desc_fields": list(DESC_FIELDS), "answer_fields": list(ANSWER_FIELDS), "runs": runs, "rows": rows}
+
+
+def dump_plan_table(table: dict) -> str:
+    """The golden's text: one row per line."""
+    import json
+    head = {k: v for k, v in table.items() if k != "rows"}
+    lines = ",\n".join(json.dumps(r, separators=(",", ":")) for r in table["rows"])
+    return json.dumps(head, indent=1)[:-2] + ',\n "rows": [\n' + lines + "\n ]\n}\n"
+
+
+if __name__ == "__main__":
+    import pathlib
+    pathlib.Path(__file__).parent.joinpath("golden", "conv_plan_table.json").write_text(dump_plan_table(plan_table()))

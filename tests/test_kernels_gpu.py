@@ -913,6 +913,75 @@ def test_groupnorm_one_call(dev, n, h, c0, c1, groups, silu, eps):
     assert torch.equal(out, again)
 
 
+def ran_as_reported(rec, n, h, w, c0, cout, ksize, **shape):
+    """The one conv recorded by rec (ops.record_conv_plans) ran the (tile, K slices) that c2d_conv2d_igemm_plan
+    answers for its shape-only descriptor with a workspace granted, and allocated the bytes that
+    c2d_conv2d_igemm_workspace_size answers for it; -> that plan."""
+    import ctypes
+    from clap2diffusion_amd import _lib
+    d = ops._shape_desc(n, h, w, c0, cout, ksize, operands=True, **shape)
+    rc, tile, split = ops._plan_query(d)
+    assert rc == 0 and rec.plans == [(tile, split)], (rc, tile, split, rec.plans)
+    assert rec.ws_bytes == [_lib.lib().c2d_conv2d_igemm_workspace_size(ctypes.byref(d))], rec.ws_bytes
+    return tile, split
+
+
+@pytest.mark.parametrize("n,h,cin,cout,padded,plan,slabs", [
+    (2, 8, 1280, 1280, False, (81, 12), 12),   # the measured table's plan: the split-K combine runs
+    (2, 16, 640, 1280, True, (44, 10), 10),    # row ring: the slice count of rr_slices, moments from the combine
+])
+def test_conv_runs_the_reported_plan(dev, n, h, cin, cout, padded, plan, slabs):
+    """c2d_conv2d_igemm runs what the plan and workspace queries report (igemm.hip resolve()): a 3x3 with a
+    residual, on the zero-bordered source also asked for its output's GroupNorm moments.  test_conv_quantisation_tail
+    checks the same of the tail split; the numerics bar is every conv's."""
+    x = gen(n, cin, h, h, seed=401)
+    w = gen(cout, cin, 3, 3, seed=402, scale=1.0 / math.sqrt(9 * cin))
+    b = gen(cout, seed=403)
+    r = gen(n, cout, h, h, seed=404)
+    ref = F.conv2d(x.half().float(), w, b, padding=1) + r.half().float()
+    wp, kp = ops.pack_conv_weight(w)
+    xd = F.pad(nhwc(x), (0, 0, 1, 1, 1, 1)) if padded else nhwc(x)
+    rec = ops.record_conv_plans()
+    with rec:
+        out = ops.conv(xd.half().to(dev), wp.to(dev), kp, cout, ksize=3, bias=b.float().to(dev),
+                       resid=nhwc(r).half().to(dev), padded=padded, gn_moments=32 if padded else 0)
+    if padded:
+        out, mom = out
+        assert mom is not None and mom.rows == 16, mom and mom.rows
+    assert ran_as_reported(rec, n, h, h, cin, cout, 3, src_pad=padded, resid=True) == plan
+    assert rec.ws_bytes == [slabs * n * h * h * cout * 4]
+    close(nchw(out), ref)
+
+
+def test_linear_runs_the_reported_plan(dev):
+    """The plain linear of the CLIP text tower's fused QKV at the CFG pair (154 rows, 768 -> 2304)."""
+    m, k, cout = 154, 768, 2304
+    x, w, b = gen(m, k, seed=411), gen(cout, k, seed=412, scale=1.0 / math.sqrt(k)), gen(cout, seed=413)
+    wp, kp = ops.pack_linear_weight(w)
+    rec = ops.record_conv_plans()
+    with rec:
+        out = ops.conv(x.half().to(dev), wp.to(dev), kp, cout, ksize=1, bias=b.float().to(dev))
+    ran_as_reported(rec, 1, 1, m, k, cout, 1)
+    close(out, x.half().float() @ w.t() + b)
+
+
+def test_lnfold_geglu_runs_the_reported_plan(dev):
+    """The panel GEMM under C2D_PRO_LNFOLD (level 0's norm3 -> GEGLU at 2048 rows): tile 70, one slice, no workspace."""
+    m, c, cout = 2048, 320, 2560
+    x = gen(m, c, seed=421) + gen(m, 1, seed=422) * 3.0
+    gamma, beta = 1.0 + 0.2 * gen(c, seed=423), 0.2 * gen(c, seed=424)
+    w, b = gen(cout, c, seed=425, scale=1.0 / math.sqrt(c)), 0.1 * gen(cout, seed=426)
+    hh, gg = (F.layer_norm(x.half().float(), (c,), gamma, beta, 1e-5) @ w.t() + b).chunk(2, -1)
+    wp, kp = ops.pack_linear_weight(ops.geglu_interleave(w, b)[0])
+    wf, bf = ops.fold_layernorm(wp, ops.geglu_interleave(w, b)[1], gamma, beta, c)
+    rec = ops.record_conv_plans()
+    with rec:
+        out = ops.conv(x.half().to(dev), wf.to(dev), kp, cout, ksize=1, bias=bf.to(dev), act="geglu", ln_fold=1e-5)
+    assert ran_as_reported(rec, 1, 1, m, c, cout, 1, act="geglu", out_ld=cout // 2, lnfold=True) == (70, 1)
+    assert rec.ws_bytes == [0]
+    close(out, hh * F.gelu(gg))
+
+
 # Quantisation tail (igemm.hip tail_images): c5's level-0 convs plan one K slice on 288 tiles of
 # 256 x 320, so the first 7 images run that plan and the 8th its own -- every per-image pointer of
 # the tail launch (both sources, the time embedding, the residual, the output; the zero-bordered
@@ -941,7 +1010,8 @@ def test_conv_quantisation_tail(dev, c0, c1, res, tmb, padded):
     xd = nhwc(x).half().to(dev)
     kw = dict(bias=b.float().to(dev), resid=nhwc(r).half().to(dev) if res else None,
               temb=te.half().to(dev) if tmb else None)
-    with ops.record_conv_plans() as plans:
+    rec = ops.record_conv_plans()
+    with rec as plans:
         if padded:
             xp = F.pad(xd.permute(0, 3, 1, 2), (1, 1, 1, 1)).permute(0, 2, 3, 1).contiguous()
             out = ops.conv(xp, wp.to(dev), kp, cout, ksize=3, padded=True, **kw)
@@ -949,8 +1019,10 @@ def test_conv_quantisation_tail(dev, c0, c1, res, tmb, padded):
             x0, x1 = (xd[..., :c0].contiguous(), xd[..., c0:].contiguous()) if c1 else (xd, None)
             out = ops.conv(x0, wp.to(dev), kp, cout, ksize=3, x2=x1, **kw)
     assert plans == [(40, 1)], plans
+    # the head's plan is the one reported; the workspace the call allocated is the tail's
+    assert ran_as_reported(rec, n, h, h, c0, cout, 3, c1=c1, src_pad=padded, resid=res, temb=tmb) == (40, 1)
     if c1:   # the tail image's own plan splits K 3 ways into the workspace the call allocated
-        assert ops.conv_workspace_bytes(n, h, h, c0, c1, cout, 3) == 3 * h * h * cout * 4
+        assert ops.conv_workspace_bytes(n, h, h, c0, c1, cout, 3) == 3 * h * h * cout * 4 == rec.ws_bytes[0]
     close(nchw(out), ref)
 
 

@@ -98,3 +98,25 @@ def test_gn_moment_rows(n, h, cin, cout, resid, temb, groups, want):
     -- the one-slice row-ring plans with the workgroup-image epilogue -- as ops.gn_moment_rows asks it."""
     from clap2diffusion_amd import ops
     assert ops.gn_moment_rows(n, h, h, cin, cout, 3, 1, True, resid, temb, groups) == want
+
+
+def test_plan_table_is_unchanged():
+    """Every answer of the three host queries (c2d_conv2d_igemm_plan without, with and with a one-byte-short
+    workspace; c2d_conv2d_igemm_workspace_size; c2d_conv2d_gn_rows with and without a residual) for every distinct
+    conv / linear descriptor of the UNet at 8x8, 16x16 and 64x64 (n = 2), 64x64 (n = 32) and 96x96 (n = 16), the
+    VAE decoder and encoder at 8x8 and 64x64 (n = 1), the decoder at 64x64 (n = 8) and the towers' linears, the 3x3
+    rows also with src_pad = 1 and under every forced (tile, split) (no run's sweep had to be dropped for size);
+    and the digest of each run's launch keys, which the Python-side queries (ops.rowring_conv, panel_gemm,
+    upfold_ok, gn_moment_rows) decide.  tests/golden/conv_plan_table.json was recorded before the planner's host
+    code was gathered into one resolved plan (python -m tests.small_shape_trace rewrites it): no row may differ."""
+    import json
+    from pathlib import Path
+
+    from tests import small_shape_trace as T
+    gold = json.loads((Path(__file__).parent / "golden" / "conv_plan_table.json").read_text())
+    table = json.loads(T.dump_plan_table(T.plan_table()))
+    assert table["desc_fields"] == gold["desc_fields"] and table["answer_fields"] == gold["answer_fields"]
+    assert table["runs"] == gold["runs"]
+    assert len(table["rows"]) == len(gold["rows"])
+    differing = [(g["d"], g, r) for g, r in zip(gold["rows"], table["rows"]) if g != r]
+    assert not differing, f"{len(differing)} rows differ, the first: {differing[0]}"
