@@ -110,9 +110,19 @@ class VAEDecoder(nn.Module):
             raise KeyError(f"unused VAE keys: {left[:4]}")
         self.decoder.mid_block.attentions[0].finalize()
 
+    @staticmethod
+    def check_size(h: int, w: int) -> None:
+        if h <= 0 or w <= 0 or (h * w) % 64:
+            raise ValueError(f"VAE decoder latents need h * w a positive multiple of 64, got {h} x {w} "
+                             "(the mid-block attention runs h * w tokens on 64-row GEMM tiles)")
+
     @torch.no_grad()
-    def forward(self, latents: torch.Tensor) -> torch.Tensor:
-        """latents [B,4,h,w] fp32 -> uint8 image NHWC [B, 8h, 8w, 3]."""
+    def decode_nhwc(self, latents: torch.Tensor) -> torch.Tensor:
+        """latents [B,4,h,w] fp32 -> conv_out's fp16 NHWC [B, 8h, 8w, 4]: RGB in [-1, 1] before the clamp, and
+        the zero pad channel."""
+        if latents.dim() != 4 or latents.shape[1] != 4:
+            raise ValueError(f"latents must be [B, 4, h, w], got {tuple(latents.shape)}")
+        self.check_size(latents.shape[2], latents.shape[3])
         d = self.decoder
         z = ops.latent_to_nhwc((latents.float() / SCALING).contiguous(), 8, dup=False)
         x = d.conv_in(self.post_quant_conv(z))
@@ -124,9 +134,18 @@ class VAEDecoder(nn.Module):
                 x = r(x)
             if hasattr(blk, "upsamplers"):
                 x = blk.upsamplers[0](x)
-        x = d.conv_out(d.conv_norm_out.apply(x, silu=True))
+        return d.conv_out(d.conv_norm_out.apply(x, silu=True))
+
+    @staticmethod
+    def quantize(x: torch.Tensor) -> torch.Tensor:
+        """decode_nhwc's [B, H, W, 4] -> uint8 [B, H, W, 3]: (x / 2 + 0.5) clamped to [0, 1], times 255, rounded."""
         img = (x[..., :3].float() / 2 + 0.5).clamp_(0, 1)
         return (img * 255).round_().to(torch.uint8)
+
+    @torch.no_grad()
+    def forward(self, latents: torch.Tensor) -> torch.Tensor:
+        """latents [B,4,h,w] fp32 -> uint8 image NHWC [B, 8h, 8w, 3]."""
+        return self.quantize(self.decode_nhwc(latents))
 
 
 class EncoderDownsample2D(nn.Module):
