@@ -545,6 +545,24 @@ class UNet2DConditionModel(nn.Module):
         return ops.conv(temb, self.w_temb_all, self.temb_kpad, self.temb_total, ksize=1, bias=self.b_temb_all,
                         silu_in=True)
 
+    def execution_order(self) -> list:
+        """The names of the stages forward_nhwc runs, in order, read off the module tree: 'time', 'conv_in', every
+        '<block>.resnets.j' / '.attentions.j' / '.downsamplers.0' / '.upsamplers.0', 'conv_norm_out+conv_out'
+        (the block-by-block tests walk the same list)."""
+        names = ["time", "conv_in"]
+        blocks = ([(f"down_blocks.{i}", b) for i, b in enumerate(self.down_blocks)] + [("mid_block", self.mid_block)] +
+                  [(f"up_blocks.{i}", b) for i, b in enumerate(self.up_blocks)])
+        for pre, blk in blocks:
+            if pre == "mid_block":
+                names += [f"{pre}.resnets.0", f"{pre}.attentions.0", f"{pre}.resnets.1"]
+                continue
+            for j in range(len(blk.resnets)):
+                names.append(f"{pre}.resnets.{j}")
+                if len(blk.attentions):
+                    names.append(f"{pre}.attentions.{j}")
+            names += [f"{pre}.{s}.0" for s in ("downsamplers", "upsamplers") if hasattr(blk, s)]
+        return names + ["conv_norm_out+conv_out"]
+
     def cfg_shared_prefix_ok(self) -> bool:
         """The [uncond, cond] halves of a CFG batch see the same latent, timestep and (per the
         composition contract) audio tokens; they first differ at the first cross-attention,
