@@ -29,6 +29,7 @@ EXPORTS = [
     "c2d_image_to_nhwc", "c2d_vae_posterior_noise",
     "c2d_cfg_ddim_step_masked", "c2d_mask_to_latent", "c2d_composite_u8",
     "c2d_inpaint_prepare",
+    "c2d_cfg_dpm_step", "c2d_cfg_dpm_step_masked",
     "c2d_clip_preprocess", "c2d_cosine_rows",
 ]
 
@@ -101,6 +102,8 @@ def lib() -> ctypes.CDLL:
         "c2d_mask_to_latent": ([vp, i, i, i, vp, vp], i),
         "c2d_composite_u8": ([vp, vp, vp, sz, vp, vp], i),
         "c2d_inpaint_prepare": ([vp, i, vp, vp, vp, vp, vp, i, i, i, i, f, vp, vp, vp, vp], i),
+        "c2d_cfg_dpm_step": ([vp, vp, vp, i, i, i, f, vp, vp, vp, i, vp], i),
+        "c2d_cfg_dpm_step_masked": ([vp, vp, vp, vp, vp, vp, i, i, i, f, vp, vp, vp, i, vp], i),
         "c2d_clip_preprocess": ([vp, i, i, i, i, i, ctypes.POINTER(c_float), ctypes.POINTER(c_float), i, vp, vp], i),
         "c2d_cosine_rows": ([vp, vp, i, i, vp, vp], i),
         "c2d_add": ([vp, vp, vp, sz, vp], i),

@@ -279,6 +279,54 @@ __global__ void cfg_ddim_masked_kernel(const f16x4* __restrict__ eps, float* x, 
     }
 }
 
+// The DPM-Solver++(2M) step's last launch: classifier-free guidance and the multistep update, and with MASKED
+// the inpainting blend on top of the identical arithmetic (a pixel with mask 1 gets the unmasked kernel's bits).
+// Contraction is off and every rounding is written out, so the two instantiations cannot fuse differently.
+// One thread per (image, latent pixel), as cfg_ddim_masked_kernel: one 8-byte load each of the uncond and cond
+// eps pixel, four channel updates with coalesced fp32 accesses.  x and x0_prev are read and written in place
+// (each thread its own elements), so neither carries __restrict__.  mcoef row (c2d.h): alpha_s, sigma_s, alpha_t,
+// sigma_t, sigma_t / sigma_s, alpha_t (1 - exp(-h)), 1 / (2 r), order.
+template <bool MASKED>
+__global__ void cfg_dpm_kernel(const f16x4* __restrict__ eps, float* x, float* x0_prev,
+                               const float* __restrict__ z0, const float* __restrict__ noise,
+                               const float* __restrict__ mask, int b, int hw, int steps, float gsc,
+                               const float* __restrict__ mcoef, const int* __restrict__ step_index,
+                               const int* __restrict__ first_step) {
+#pragma clang fp contract(off)
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)b * hw) return;
+    const int st = *step_index;
+    if ((unsigned)st >= (unsigned)steps) return;   // a counter outside the table: nothing is read or written
+    const size_t bi = i / hw, p = i - bi * hw;
+    const float* row = mcoef + (size_t)st * 8;
+    const float alpha_s = row[0], sigma_s = row[1], alpha_t = row[2], sigma_t = row[3];
+    const float ratio = row[4], gain = row[5], inv2r = row[6];
+    const bool first_order = st == *first_step || row[7] == 1.0f;   // x0_prev is not read then: it may hold anything
+    const bool last = st == steps - 1;
+    const f16x4 vu = eps[i], vc = eps[(size_t)b * hw + i];
+    float m = 1.0f;
+    if constexpr (MASKED) m = mask[i];
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch) {
+        const size_t j = (bi * 4 + ch) * hw + p;
+        const float eu = (float)vu[ch];
+        const float ec = (float)vc[ch];
+        const float e = eu + gsc * (ec - eu);
+        const float xv = x[j];
+        const float x0 = (xv - sigma_s * e) / alpha_s;
+        float d = x0;
+        if (!first_order) d = x0 + (x0 - x0_prev[j]) * inv2r;
+        float xn = ratio * xv + gain * d;
+        if constexpr (MASKED) {
+            const float z = z0[j];
+            const float known = last ? z : alpha_t * z + sigma_t * noise[j];
+            xn = (1.0f - m) * known + m * xn;
+        }
+        x0_prev[j] = x0;
+        x[j] = xn;
+    }
+}
+
 // uint8 mask [n][8h][8w] -> fp32 [n][h][w]: the sample at (8y, 8x) (F.interpolate nearest at an exact factor 8),
 // binarised at 128
 __global__ void mask_to_latent_kernel(const uint8_t* __restrict__ mask, int n, int h, int w, float* __restrict__ out) {
@@ -576,6 +624,51 @@ extern "C" int c2d_cfg_ddim_step_masked(const void* eps, float* x, const float* 
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(cfg_ddim_masked_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s,
                        (const f16x4*)eps, x, z0, noise, mask, b, hw, steps, guidance, coef, step_index);
+    if (advance) hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, step_index);
+    return check_launch();
+}
+
+// The checks c2d_cfg_dpm_step and c2d_cfg_dpm_step_masked share; tot = b * hw on success.
+static int cfg_dpm_check(const void* eps, const float* x, const float* x0_prev, int b, int hw, int steps,
+                         const float* mcoef, const int* step_index, const int* first_step, size_t* tot) {
+    if (!eps || !x || !x0_prev || !mcoef || !step_index || !first_step) return C2D_E_ARG;
+    if (b <= 0 || hw <= 0 || steps <= 0) return C2D_E_SHAPE;
+    *tot = (size_t)b * hw;
+    if (*tot > (size_t)INT32_MAX / 4) return C2D_E_SHAPE;   // b * 4 * hw elements stay below 2^31
+    const uintptr_t xa = (uintptr_t)x, pa = (uintptr_t)x0_prev, bytes = (uintptr_t)*tot * 4 * sizeof(float);
+    if (xa < pa + bytes && pa < xa + bytes) return C2D_E_ARG;   // both are read and written: they must not overlap
+    if (((uintptr_t)eps & 7) || ((xa | pa | (uintptr_t)mcoef | (uintptr_t)step_index | (uintptr_t)first_step) & 3))
+        return C2D_E_ALIGN;
+    return C2D_OK;
+}
+
+extern "C" int c2d_cfg_dpm_step(const void* eps, float* x, float* x0_prev, int b, int hw, int steps, float guidance,
+                                const float* mcoef, int* step_index, const int* first_step, int advance,
+                                void* stream) {
+    size_t tot = 0;
+    const int rc = cfg_dpm_check(eps, x, x0_prev, b, hw, steps, mcoef, step_index, first_step, &tot);
+    if (rc != C2D_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(cfg_dpm_kernel<false>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s,
+                       (const f16x4*)eps, x, x0_prev, (const float*)nullptr, (const float*)nullptr,
+                       (const float*)nullptr, b, hw, steps, guidance, mcoef, step_index, first_step);
+    if (advance) hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, step_index);
+    return check_launch();
+}
+
+extern "C" int c2d_cfg_dpm_step_masked(const void* eps, float* x, float* x0_prev, const float* z0,
+                                       const float* noise, const float* mask, int b, int hw, int steps,
+                                       float guidance, const float* mcoef, int* step_index, const int* first_step,
+                                       int advance, void* stream) {
+    if (!z0 || !noise || !mask) return C2D_E_ARG;
+    size_t tot = 0;
+    const int rc = cfg_dpm_check(eps, x, x0_prev, b, hw, steps, mcoef, step_index, first_step, &tot);
+    if (rc != C2D_OK) return rc;
+    if (((uintptr_t)z0 | (uintptr_t)noise | (uintptr_t)mask) & 3) return C2D_E_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(cfg_dpm_kernel<true>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s,
+                       (const f16x4*)eps, x, x0_prev, z0, noise, mask, b, hw, steps, guidance, mcoef, step_index,
+                       first_step);
     if (advance) hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, step_index);
     return check_launch();
 }

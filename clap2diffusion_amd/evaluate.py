@@ -52,11 +52,12 @@ def image_to_u8(image) -> torch.Tensor:
 
 class Evaluator:
     def __init__(self, checkpoint_dir="../checkpoints", pipeline=None, scorer=None, clip_model_path=None,
-                 batch: int = 4, **pipeline_kwargs):
+                 batch: int = 4, sampler: str | None = None, **pipeline_kwargs):
         """pipeline / scorer: injected instances (tests, or a pipeline that is already loaded); by default the
         pipeline is AudioToImageInference(checkpoint_dir, **pipeline_kwargs) and the scorer a ClipScorer built on
         first use from clip_model_path (None: the seeded recipe) with the pipeline's tokenizer.  batch: requests
-        per generate call in evaluate_dataset."""
+        per generate call in evaluate_dataset.  sampler: passed to every generate call as sampler= when given
+        (None: the pipeline's default, DDIM)."""
         self.checkpoint_dir = Path(checkpoint_dir)
         if pipeline is None:
             from .pipeline import AudioToImageInference
@@ -65,6 +66,7 @@ class Evaluator:
         self._scorer = scorer
         self.clip_model_path = clip_model_path
         self.batch = max(1, int(batch))
+        self.generate_kwargs = {"sampler": sampler} if sampler is not None else {}
 
         self.metrics = {name: [] for name in METRIC_NAMES}
 
@@ -87,7 +89,7 @@ class Evaluator:
     def evaluate_single(self, audio_path, text_prompt, reference_image=None):
         """One request -> {"clip_score", "generated_image" (PIL)} and, with a reference image (a PIL image, a path
         or a uint8 array of any size), "image_similarity"."""
-        images = self.pipeline.batch_generate_u8([audio_path], [text_prompt], seed=EVAL_SEED)
+        images = self.pipeline.batch_generate_u8([audio_path], [text_prompt], seed=EVAL_SEED, **self.generate_kwargs)
         result = {"clip_score": self._scores(images, [text_prompt])[0],
                   "generated_image": self.pipeline.to_pil(images)[0]}
         if reference_image is not None:
@@ -123,7 +125,7 @@ class Evaluator:
         for start in range(0, len(found), self.batch):
             chunk = found[start:start + self.batch]
             texts = [entry["text"] for entry, _ in chunk]
-            images = self.pipeline.batch_generate_u8([path for _, path in chunk], texts, seed=EVAL_SEED)
+            images = self.pipeline.batch_generate_u8([path for _, path in chunk], texts, seed=EVAL_SEED, **self.generate_kwargs)
             scores = self._scores(images, texts)
             for (entry, _), score, pil in zip(chunk, scores, self.pipeline.to_pil(images)):
                 pil.save(output_dir / f"{entry['id']}_generated.png")

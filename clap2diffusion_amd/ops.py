@@ -570,6 +570,46 @@ def cfg_ddim_step_masked(eps: torch.Tensor, x: torch.Tensor, z0: torch.Tensor, n
     return x
 
 
+def _check_dpm_step(eps, x, x0_prev, mcoef, step_index, first_step) -> None:
+    _require(x, "x")
+    assert eps.dtype == F16 and eps.is_contiguous() and eps.numel() == 2 * x.numel()
+    assert x.dim() == 4 and x.shape[1] == 4
+    for t in (x, x0_prev):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape and t.is_cuda
+    assert x0_prev is not x
+    assert mcoef.dtype == torch.float32 and mcoef.is_contiguous() and mcoef.dim() == 2 and mcoef.shape[1] == 8
+    for t in (step_index, first_step):
+        assert t.dtype == torch.int32 and t.numel() == 1
+
+
+def cfg_dpm_step(eps: torch.Tensor, x: torch.Tensor, x0_prev: torch.Tensor, guidance: float, mcoef: torch.Tensor,
+                 step_index: torch.Tensor, first_step: torch.Tensor, advance: bool = True) -> torch.Tensor:
+    """The DPM-Solver++(2M) step's update of x fp32 [B, 4, h, w] in place (c2d::cfg_dpm_step): classifier-free
+    guidance over eps fp16 NHWC [2B, h, w, 4], then the multistep update from mcoef fp32 [steps, 8]
+    (DPMSolverMultistepScheduler.device_tables) at the device counter step_index.  x0_prev (fp32, x's shape) is
+    the previous step's data prediction, overwritten with this step's; the step equal to the device int32
+    first_step is first-order and does not read it."""
+    _check_dpm_step(eps, x, x0_prev, mcoef, step_index, first_step)
+    C2D.cfg_dpm_step(eps, x, x0_prev, float(guidance), mcoef, step_index, first_step, bool(advance))
+    return x
+
+
+def cfg_dpm_step_masked(eps: torch.Tensor, x: torch.Tensor, x0_prev: torch.Tensor, z0: torch.Tensor,
+                        noise: torch.Tensor, mask: torch.Tensor, guidance: float, mcoef: torch.Tensor,
+                        step_index: torch.Tensor, first_step: torch.Tensor, advance: bool = True) -> torch.Tensor:
+    """cfg_dpm_step for inpainting (c2d::cfg_dpm_step_masked): its result where mask fp32 [B, h, w] is 1, the
+    original z0 re-noised with `noise` to the next step's timestep (z0 itself at the last step) where it is 0, the
+    blend in between."""
+    _check_dpm_step(eps, x, x0_prev, mcoef, step_index, first_step)
+    for t in (z0, noise):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape and t.is_cuda
+    assert mask.dtype == torch.float32 and mask.is_contiguous() and mask.is_cuda
+    assert tuple(mask.shape) == (x.shape[0], x.shape[2], x.shape[3])
+    C2D.cfg_dpm_step_masked(eps, x, x0_prev, z0, noise, mask, float(guidance), mcoef, step_index, first_step,
+                            bool(advance))
+    return x
+
+
 def mask_to_latent(mask_u8: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """uint8 [N, H, W] (H, W multiples of 8; >= 128 = repaint) -> fp32 [N, H/8, W/8] of 0 / 1: the sample at
     (8y, 8x), i.e. the binarised mask under F.interpolate nearest (c2d::mask_to_latent)."""

@@ -36,7 +36,7 @@ from .image_io import prepare_image_array, prepare_mask_array
 from .processor import AudioProcessorManager
 from .projectors import AudioAdapter, HierarchicalAudioV4, ImprovedHierarchicalAudioEncoder, normalize_tokens
 from .sampler import GraphDenoiser
-from .scheduler import DDIMScheduler
+from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler
 from .text_encoder import TextEncoder, make_tokenizer
 from .unet import UNet2DConditionModel
 from .vae import VAEDecoder, VAEEncoder
@@ -48,6 +48,17 @@ from . import ops
 # (tests/test_small_shapes_gpu.py, DESIGN.md "Smallest supported shapes").
 IMAGE_SIZE_MULTIPLE = 64
 MIN_IMAGE_SIZE = 64
+
+
+# sampler= names: the solver of the denoise loop.  Both run on DDIMScheduler's timestep grid.
+SAMPLERS = {"ddim": DDIMScheduler, "dpmpp_2m": DPMSolverMultistepScheduler}
+
+
+def check_sampler(sampler: str) -> str:
+    """ValueError unless `sampler` names a solver the pipeline runs."""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"unknown sampler {sampler!r}: choose one of {', '.join(SAMPLERS)}")
+    return sampler
 
 
 def check_image_size(height: int, width: int) -> None:
@@ -278,15 +289,16 @@ class AudioToImageInference:
     @torch.no_grad()
     def _generate_u8(self, audio_paths, text_prompts, num_inference_steps=50, guidance_scale=7.5, seed=None,
                      use_hierarchical=True, init_images=None, strength=0.8, sample_posterior=True, masks=None,
-                     composite=True, **_):
+                     composite=True, sampler="ddim", **_):
         """generate() for a list of requests -> generate_batch's uint8 [B, H, W, 3] device tensor; keywords it does
         not know are ignored."""
+        check_sampler(sampler)   # before any work on the audio
         mel = self.mel_features([self.load_audio(p) for p in audio_paths])
         lat, eps = self._request_latents(len(audio_paths), seed, with_eps=init_images is not None)
         return self.generate_batch(mel, list(text_prompts), num_inference_steps, guidance_scale,
                                    use_hierarchical=use_hierarchical, latents=lat, init_images=init_images,
                                    strength=strength, posterior_eps=eps if sample_posterior else None, masks=masks,
-                                   composite=composite)
+                                   composite=composite, sampler=sampler)
 
     def _generate(self, audio_paths, text_prompts, *args, **kwargs):
         """_generate_u8 -> PIL images."""
@@ -294,23 +306,25 @@ class AudioToImageInference:
 
     def generate(self, audio_path, text_prompt="", num_inference_steps=50, guidance_scale=7.5, seed=None,
                  use_hierarchical=True, init_image=None, strength=0.8, sample_posterior=True, mask=None,
-                 composite=True):
+                 composite=True, sampler="ddim"):
         """init_image (a PIL image, a path or a uint8 tensor [1, H, W, 3]): audio-guided image-to-image, the
         schedule entered at DDIMScheduler.img2img_start(steps, strength) from the encoded image plus scheduled
         noise; sample_posterior=False takes the VAE posterior's mode instead of a sample.
         mask (prepare_mask_array forms; >= 128 = repaint, < 128 = keep) with init_image: audio-guided inpainting
         (diffusers StableDiffusionInpaintPipeline with a 4-channel UNet): after every step the kept latents are
         set back to the image's, re-noised to that step; strength 1 starts from pure noise.  composite: the kept
-        pixels of the result are the init image's own bytes, else the plain decode."""
+        pixels of the result are the init image's own bytes, else the plain decode.
+        sampler: "ddim" (the default) or "dpmpp_2m", DPM-Solver++(2M) on the same timestep grid (usually run at
+        20-25 steps); anything else is a ValueError."""
         return self._generate([audio_path], [text_prompt], num_inference_steps, guidance_scale, seed, use_hierarchical,
-                              init_image, strength, sample_posterior, mask, composite)[0]
+                              init_image, strength, sample_posterior, mask, composite, sampler=sampler)[0]
 
     def batch_generate(self, audio_paths, text_prompts=None, **kwargs):
         """The reference runs generate(path, prompt, **kwargs) per item (scripts/inference.py:168-180),
         so every item is re-seeded with the same seed (the same initial noise for every item) and
         seed=None leaves the RNG unseeded; here the items run as one batch with those latents.
-        init_images= and masks= (one per item, or one for all), strength=, sample_posterior=, composite= as
-        generate()."""
+        init_images= and masks= (one per item, or one for all), strength=, sample_posterior=, composite=, sampler=
+        as generate()."""
         return self.to_pil(self.batch_generate_u8(audio_paths, text_prompts, **kwargs))
 
     def batch_generate_u8(self, audio_paths, text_prompts=None, **kwargs) -> torch.Tensor:
@@ -326,15 +340,15 @@ class AudioToImageInference:
         return initial_latents(seeds, self.height // 8, self.width // 8, self.device)
 
     def denoiser(self, b: int, steps: int, guidance: float, ehs, audio_kwargs, latent_hw=None,
-                 slot: int = 0) -> GraphDenoiser:
-        """The captured-graph denoise loop for (batch, steps, guidance, latent size), built once;
+                 slot: int = 0, sampler: str = "ddim") -> GraphDenoiser:
+        """The captured-graph denoise loop for (batch, steps, guidance, latent size, sampler), built once;
         `slot` keeps separate sampler states for batches run concurrently on different streams."""
         h, w = latent_hw or (self.height // 8, self.width // 8)
         check_latent_size(h, w)   # latent_hw= and caller-supplied latents (generate_batch, BatchGraph) come through here
-        key = (b, steps, float(guidance), h, w, slot)
+        key = (b, steps, float(guidance), h, w, slot, check_sampler(sampler))
         d = self._denoisers.get(key)
         if d is None:
-            sch = DDIMScheduler()
+            sch = SAMPLERS[sampler]()
             sch.set_timesteps(steps)
             d = GraphDenoiser(self.unet, sch, b, h, w, guidance, ehs, audio_kwargs, use_graph=self.use_graph)
             self._denoisers[key] = d
@@ -363,7 +377,8 @@ class AudioToImageInference:
                        guidance_scale: float = 7.5, seeds: list[int] | None = None, use_hierarchical: bool = True,
                        ids: tuple | None = None, latents: torch.Tensor | None = None, init_images=None,
                        strength: float = 0.8, posterior_eps: torch.Tensor | None = None,
-                       sample_posterior: bool = True, masks=None, composite: bool = True) -> torch.Tensor:
+                       sample_posterior: bool = True, masks=None, composite: bool = True,
+                       sampler: str = "ddim") -> torch.Tensor:
         """mel [B, 1001, 64] on device -> uint8 images NHWC [B, H, W, 3] on device.  The
         image size follows the latents ([B, 4, H/8, W/8]; default: the pipeline's size).
         init_images (prepare_images forms; the pipeline's size): image-to-image.  The images are encoded, the
@@ -375,7 +390,10 @@ class AudioToImageInference:
         (c2d_inpaint_prepare) writes the sampler's z0 (the scaled posterior sample or mode), its first latents (z0
         noised to timesteps[t_start], or `latents` themselves when t_start is 0) and its latent mask; the masked
         step (c2d_cfg_ddim_step_masked) runs steps - t_start times; with composite the kept pixels of the decode are
-        set back to the init images' bytes (c2d_composite_u8)."""
+        set back to the init images' bytes (c2d_composite_u8).
+        sampler "dpmpp_2m": the same loop on a denoiser of its own whose step ends with c2d_cfg_dpm_step
+        (c2d_cfg_dpm_step_masked with masks)."""
+        check_sampler(sampler)
         b = mel.shape[0]
         req = self._resolve(b, num_inference_steps, init_images, strength, masks, composite)
         seeds = seeds if seeds is not None else list(range(b))
@@ -388,7 +406,8 @@ class AudioToImageInference:
         if ids is None:
             ids = (self.tokenizer([""] * b, self.device), self.tokenizer(prompts or [""] * b, self.device))
         ehs, kw, _ = self.condition(mel, ids[0], ids[1], use_hierarchical)
-        den = self.denoiser(b, num_inference_steps, guidance_scale, ehs, kw, latent_hw=tuple(latents.shape[-2:]))
+        den = self.denoiser(b, num_inference_steps, guidance_scale, ehs, kw, latent_hw=tuple(latents.shape[-2:]),
+                            sampler=sampler)
         den.ehs.copy_(ehs)
         for k, v in kw["audio"].items():
             den.kw["audio"][k].copy_(v)
@@ -408,7 +427,7 @@ class AudioToImageInference:
                                guidance_scale: float = 7.5, use_hierarchical: bool = True,
                                slot: int = 0, init_images: torch.Tensor | None = None, strength: float = 0.8,
                                posterior_eps: torch.Tensor | None = None, masks=None,
-                               composite: bool = True) -> torch.Tensor:
+                               composite: bool = True, sampler: str = "ddim") -> torch.Tensor:
         """generate_batch from device-resident inputs (48 kHz clips concatenated + offsets /
         lengths, token ids, latents) as hipGraphs: one graph for the conditioning leg, the
         denoise-step graph replayed per DDIM step, one graph for the VAE decode (BatchGraph).
@@ -421,15 +440,17 @@ class AudioToImageInference:
         masks (uint8 [B, H, W] on the device, or any prepare_mask_array form) with init_images: inpainting.  The
         conditioning graph then ends with c2d_inpaint_prepare over static image and mask buffers, the steps
         replay the sampler's masked graph, and with composite the decode graph ends with c2d_composite_u8; a
-        call with another image or mask copies it into the static buffers and replays the same graphs."""
+        call with another image or mask copies it into the static buffers and replays the same graphs.
+        sampler as generate_batch; it is part of the graphs' key, so the two solvers never share state."""
+        check_sampler(sampler)
         req = self._resolve(offsets.numel(), num_inference_steps, init_images, strength, masks, composite)
         key = (offsets.numel(), wave.numel(), num_inference_steps, float(guidance_scale), tuple(latents.shape),
-               bool(use_hierarchical), slot, req.masks is not None, req.composite, req.t_start, req.images is not None,
-               posterior_eps is not None)
+               bool(use_hierarchical), slot, sampler, req.masks is not None, req.composite, req.t_start,
+               req.images is not None, posterior_eps is not None)
         bg = self._batch_graphs.get(key)
         if bg is None:
             bg = BatchGraph(self, wave, offsets, lengths, ids, latents, num_inference_steps, guidance_scale,
-                            use_hierarchical, slot, req, posterior_eps)
+                            use_hierarchical, slot, req, posterior_eps, sampler)
             self._batch_graphs[key] = bg
         return bg.run(wave, offsets, lengths, ids, latents, req.images, posterior_eps, req.masks)
 
@@ -457,7 +478,8 @@ class BatchGraph:
     c2d_composite_u8 into the static image."""
 
     def __init__(self, pipe: AudioToImageInference, wave, offsets, lengths, ids, latents, steps: int,
-                 guidance: float, use_hierarchical: bool, slot: int, req: _Request, posterior_eps=None):
+                 guidance: float, use_hierarchical: bool, slot: int, req: _Request, posterior_eps=None,
+                 sampler: str = "ddim"):
         self.pipe, self.use_hier = pipe, use_hierarchical
         self.t_start, self.composite = req.t_start, req.composite
         self.masks = req.masks.clone() if req.masks is not None else None
@@ -473,7 +495,8 @@ class BatchGraph:
         # eager warm-up: builds (and captures) the denoiser, caches HTSAT tables, packs lazily
         ehs, kw, _ = pipe.condition(fe.from_device(self.wave, self.offs, self.lens, out=self.mel), self.ids_u,
                                     self.ids_c, use_hierarchical)
-        self.den = pipe.denoiser(b, steps, guidance, ehs, kw, latent_hw=tuple(self.lat.shape[-2:]), slot=slot)
+        self.den = pipe.denoiser(b, steps, guidance, ehs, kw, latent_hw=tuple(self.lat.shape[-2:]), slot=slot,
+                                 sampler=sampler)
         self.den.ehs.copy_(ehs)
         self.den.prepare_context()
         self.den.ensure_captured(self.masks is not None)
@@ -543,6 +566,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--strength", type=float, default=0.8, help="img2img strength in (0, 1]: 1 = ignore the image")
     ap.add_argument("--mask", type=str, default=None,
                     help="Inpaint --init_image: a grey-scale image, >= 128 = repaint, < 128 = keep")
+    ap.add_argument("--sampler", type=str, default="ddim", choices=sorted(SAMPLERS),
+                    help="Solver of the denoise loop: ddim, or dpmpp_2m (DPM-Solver++(2M), usually 20-25 --steps)")
     ap.add_argument("--no_composite", action="store_true",
                     help="With --mask: return the plain decode instead of pasting the kept pixels back")
     return ap
@@ -555,7 +580,8 @@ def main():
     pipe = AudioToImageInference(checkpoint_dir=a.checkpoint_dir, sd_model_path=a.sd_model, clap_model_path=a.clap_model)
     img = pipe.generate(audio_path=a.audio, text_prompt=a.text, num_inference_steps=a.steps,
                         guidance_scale=a.cfg_scale, seed=a.seed, use_hierarchical=not a.no_hierarchical,
-                        init_image=a.init_image, strength=a.strength, mask=a.mask, composite=not a.no_composite)
+                        init_image=a.init_image, strength=a.strength, mask=a.mask, composite=not a.no_composite,
+                        sampler=a.sampler)
     img.save(a.output)
     print(f"Image saved to {a.output}")
 

@@ -1,4 +1,4 @@
-"""CFG + DDIM denoise loop driven by a captured hipGraph.
+"""CFG + DDIM (or DPM-Solver++(2M)) denoise loop driven by a captured hipGraph.
 
 One denoise step = latent -> NHWC fp16 (duplicated for the [uncond, cond]
 CFG pair), sinusoidal timestep embedding, the HIP UNet forward, and the fused
@@ -17,13 +17,18 @@ step only, so one run computes it for every step at once (M = steps rows instead
 of four M = 2B launches per step, whose K loops are pure latency) and the step
 selects its row through the device step counter, broadcast to the CFG batch by a
 zero leading stride.
+
+With a DPMSolverMultistepScheduler the step ends with the fused CFG + DPM-Solver++(2M) update instead: the
+denoiser then also holds the previous step's data prediction x0_prev and a device copy of the step the run was
+entered at (first_idx: that step is first-order and does not read x0_prev), so the one captured graph serves
+text-to-image and img2img entered at any step.  Everything before the final launch is the same.
 """
 from __future__ import annotations
 
 import torch
 
 from . import ops
-from .scheduler import DDIMScheduler
+from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler
 from .vae import SCALING
 
 
@@ -39,10 +44,15 @@ class GraphDenoiser:
         self.cross_attns = [m for m in unet.modules()
                             if getattr(m, "is_cross_attention", False) and hasattr(m.processor, "context_kv")]
         self.context_kv = {}
-        self.t_table, self.coef = scheduler.device_tables(dev)
+        self.dpm = isinstance(scheduler, DPMSolverMultistepScheduler)
+        self.t_table, self.coef, *mcoef = scheduler.device_tables(dev)
         self.steps = self.t_table.numel()
         self.x = torch.zeros(batch, 4, height, width, dtype=torch.float32, device=dev)
         self.step_idx = torch.zeros(1, dtype=torch.int32, device=dev)
+        if self.dpm:   # the multistep state; a DDIM denoiser allocates none of it
+            self.mcoef, = mcoef
+            self.x0_prev = torch.zeros_like(self.x)
+            self.first_idx = torch.zeros(1, dtype=torch.int32, device=dev)
         self.use_graph = use_graph
         self.graph = None
         # inpainting: the known latents, the noise that made the initial latents and the latent mask, read by the
@@ -87,7 +97,13 @@ class GraphDenoiser:
         temb_all = self.temb_cur.expand(2 * self.b, self.temb_cur.shape[1])   # zero row stride: one row for all
         eps = self.unet.forward_nhwc(xin, None, self.ehs, dict(self.kw, context_kv=self.context_kv),
                                      temb_all=temb_all, cfg_pair=True)
-        if masked:   # inpainting: the same update blended with the known region (z0 re-noised to the next step)
+        if self.dpm and masked:
+            ops.cfg_dpm_step_masked(eps, self.x, self.x0_prev, self.z0, self.noise, self.mask, self.g, self.mcoef,
+                                    self.step_idx, self.first_idx, advance=True)
+        elif self.dpm:
+            ops.cfg_dpm_step(eps, self.x, self.x0_prev, self.g, self.mcoef, self.step_idx, self.first_idx,
+                             advance=True)
+        elif masked:   # inpainting: the same update blended with the known region (z0 re-noised to the next step)
             ops.cfg_ddim_step_masked(eps, self.x, self.z0, self.noise, self.mask, self.g, self.coef, self.step_idx,
                                      advance=True)
         else:
@@ -148,6 +164,8 @@ class GraphDenoiser:
             ops.inpaint_prepare(moments, latents, mask_u8, SCALING, eps=eps, coef=self.coef, step_index=self.step_idx,
                                 pure_noise=t_start == 0, z0=self.z0, x=self.x, mask=self.mask)
             self.noise.copy_(latents)
+        if self.dpm:   # the step the counter was just set to is this run's first: first-order, x0_prev unread
+            self.first_idx.fill_(t_start)
 
     def step(self, masked: bool = False) -> None:
         """One step: a replay of the (masked) step graph, or the eager body."""

@@ -337,6 +337,27 @@ def inpaint_prepare(moments: Tensor, eps: Optional[Tensor], noise: Tensor, mask_
                                     stream_ptr()), "c2d_inpaint_prepare")
 
 
+@custom_op("c2d::cfg_dpm_step", mutates_args=("x", "x0_prev", "step_index"), device_types=_CU)
+def cfg_dpm_step(eps: Tensor, x: Tensor, x0_prev: Tensor, guidance: float, mcoef: Tensor, step_index: Tensor,
+                 first_step: Tensor, advance: bool) -> None:
+    """c2d_cfg_dpm_step: the CFG + DPM-Solver++(2M) update of x [b][4][h][w] and x0_prev (as x); the number of
+    steps is mcoef's row count."""
+    b, _, hgt, wid = x.shape
+    check(lib().c2d_cfg_dpm_step(ptr(eps), ptr(x), ptr(x0_prev), b, hgt * wid, mcoef.shape[0], guidance, ptr(mcoef),
+                                 ptr(step_index), ptr(first_step), int(advance), stream_ptr()), "c2d_cfg_dpm_step")
+
+
+@custom_op("c2d::cfg_dpm_step_masked", mutates_args=("x", "x0_prev", "step_index"), device_types=_CU)
+def cfg_dpm_step_masked(eps: Tensor, x: Tensor, x0_prev: Tensor, z0: Tensor, noise: Tensor, mask: Tensor,
+                        guidance: float, mcoef: Tensor, step_index: Tensor, first_step: Tensor,
+                        advance: bool) -> None:
+    """c2d_cfg_dpm_step_masked: cfg_dpm_step blended with the known region (z0, noise as x; mask fp32 [b][h][w])."""
+    b, _, hgt, wid = x.shape
+    check(lib().c2d_cfg_dpm_step_masked(ptr(eps), ptr(x), ptr(x0_prev), ptr(z0), ptr(noise), ptr(mask), b, hgt * wid,
+                                        mcoef.shape[0], guidance, ptr(mcoef), ptr(step_index), ptr(first_step),
+                                        int(advance), stream_ptr()), "c2d_cfg_dpm_step_masked")
+
+
 @custom_op("c2d::clip_preprocess", mutates_args=("out",), device_types=_CU)
 def clip_preprocess(img: Tensor, size: int, patch: int, mean: list[float], std: list[float], out: Tensor) -> None:
     """c2d_clip_preprocess: uint8 [n][h][w][3] -> fp16 [n * (size / patch)^2][kpad] normalised patch rows (PIL
@@ -370,7 +391,7 @@ for _op in (pack_weights, groupnorm_stats, groupnorm_apply, groupnorm, groupnorm
             attention_small, window_attention, htsat_mel_patches, patch_merge_gather, row_mean, softmax_rows,
             l2_normalize, clap_log_mel, timestep_embedding, cfg_ddim_step, latent_to_nhwc, upsample_nearest2x, add,
             image_to_nhwc, vae_posterior_noise, cfg_ddim_step_masked, mask_to_latent, composite_u8, inpaint_prepare,
-            clip_preprocess, cosine_rows):
+            cfg_dpm_step, cfg_dpm_step_masked, clip_preprocess, cosine_rows):
     _op.register_fake(lambda *args, **kwargs: None)
 
 OPS = ("conv2d_igemm", "pack_weights", "groupnorm_stats", "groupnorm_apply", "groupnorm", "groupnorm_pad", "groupnorm_moments",
@@ -379,4 +400,4 @@ OPS = ("conv2d_igemm", "pack_weights", "groupnorm_stats", "groupnorm_apply", "gr
        "row_mean", "softmax_rows", "l2_normalize", "clap_log_mel", "timestep_embedding", "cfg_ddim_step",
        "latent_to_nhwc", "upsample_nearest2x", "add", "image_to_nhwc", "vae_posterior_noise",
        "cfg_ddim_step_masked", "mask_to_latent", "composite_u8", "inpaint_prepare",
-       "clip_preprocess", "cosine_rows")
+       "cfg_dpm_step", "cfg_dpm_step_masked", "clip_preprocess", "cosine_rows")

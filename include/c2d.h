@@ -540,6 +540,37 @@ int c2d_inpaint_prepare(const void* moments, int ld, const float* eps, const flo
                         float scaling, float* z0, float* x, float* mask, void* stream);
 
 /*
+ * DPM-Solver++(2M) (two entry points added to the r7 ABI: no struct changed).
+ *
+ * Fused classifier-free guidance + the data-prediction multistep update of Lu et al. 2022 (Algorithm 2) on the
+ * DDIM grid (clap2diffusion_amd/scheduler.py DPMSolverMultistepScheduler; not diffusers' scheduler bit for bit).
+ * eps fp16 NHWC [2b][hw][4] (uncond rows first, 8-byte aligned); x and x0_prev fp32 NCHW [b][4][hw], both read
+ * and written in place.  mcoef fp32 [steps][8], row st = *step_index:
+ *   (alpha_s, sigma_s, alpha_t, sigma_t, sigma_t / sigma_s, alpha_t (1 - exp(-h)), 1 / (2 r), order)
+ * fp32 throughout, no contraction (every product and sum rounded on its own):
+ *   e  = eps_u + g (eps_c - eps_u);   x0 = (x - sigma_s e) / alpha_s
+ *   D  = x0                                     st == *first_step, or order == 1
+ *        x0 + (x0 - x0_prev) (1 / (2 r))        otherwise
+ *   x' = (sigma_t / sigma_s) x + alpha_t (1 - exp(-h)) D;   x0_prev <- x0;   x <- x'
+ * first_step is a device int32, the step a run is entered at (0 for text-to-image, t_start for img2img): on that
+ * step x0_prev is written and never read, so it needs no clearing between runs and one captured graph serves
+ * every entry point.  A counter outside [0, steps) reads and writes nothing.  advance as in c2d_cfg_ddim_step.
+ *
+ * c2d_cfg_dpm_step_masked (inpainting): the same arithmetic (where mask is 1 the result has the unmasked entry's
+ * bits), then x <- (1 - mask) known + mask x' with z0, noise fp32 NCHW [b][4][hw] and mask fp32 [b][hw] as
+ * c2d_cfg_ddim_step_masked takes them, known = alpha_t z0 + sigma_t noise from the row, z0 itself at the last
+ * step (st == steps - 1).
+ *
+ * C2D_E_ARG: a null pointer, or x and x0_prev overlapping; C2D_E_SHAPE: b, hw or steps <= 0, or b * 4 * hw above
+ * INT32_MAX; C2D_E_ALIGN: eps not 8-byte, or an fp32 / int32 pointer not 4-byte aligned; all before any launch.
+ */
+int c2d_cfg_dpm_step(const void* eps, float* x, float* x0_prev, int b, int hw, int steps, float guidance,
+                     const float* mcoef, int* step_index, const int* first_step, int advance, void* stream);
+int c2d_cfg_dpm_step_masked(const void* eps, float* x, float* x0_prev, const float* z0, const float* noise,
+                            const float* mask, int b, int hw, int steps, float guidance, const float* mcoef,
+                            int* step_index, const int* first_step, int advance, void* stream);
+
+/*
  * CLIP-score evaluation (two entry points added to the r7 ABI: no struct changed).
  *
  * CLIPImageProcessor in one launch: resize (PIL Image.BICUBIC, shorter side to `size`), centre crop size x size,
